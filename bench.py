@@ -12,6 +12,11 @@ barrier/all-reduce for timing): weak scaling, per-GPU work fixed.
 
     python bench.py [--gpus N --steps K --warmup W]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds what
+is measured outside the timed window (the latency points under Poisson arrivals, the light-load
+point through the services, the topic-search latency); ``--dump-outputs DIR`` writes what the last
+timed step generated as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -82,7 +87,35 @@ def parse_args(argv=None):
     ap.add_argument("--pipeline", choices=["bench", "node"], default="bench",
                     help="bench: the stage code with a static LLM batch (headline); node: the real services "
                          "(Node, in-proc bus, continuous summarization engine), pipeline/node_bench.py")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the probes that take runs of their own: --latency-rate, "
+                         "--latency-low-rate, --service-latency-rate and --search-queries (all off without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one generated (token ids and prompt lengths "
+                         "per thread) as DIR/<name>.npy, float32; same arguments -> same inputs from run to run")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.pipeline == "node":
+        ap.error("--dump-outputs reads the engine of --pipeline bench; the node pipeline stores reports instead")
+    if not args.full:
+        # a plain run does only what the headline figure needs
+        args.latency_rate = args.latency_low_rate = args.service_latency_rate = 0.0
+        args.search_queries = 0
+    return args
+
+
+def dump_outputs(out_dir, res, rank, world):
+    """--dump-outputs: the arrays the last timed step's ``LLMEngine.generate`` returned -- the
+    generated token ids of every thread (one row each, -1 behind a shorter row) and the prompt
+    lengths -- as float32 (ids stay below 2**24, so they are exact)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f".rank{rank}" if world > 1 else ""
+    tokens = np.full((len(res.tokens), max((len(t) for t in res.tokens), default=0)), -1.0, dtype=np.float32)
+    for i, t in enumerate(res.tokens):
+        tokens[i, :len(t)] = t
+    np.save(os.path.join(out_dir, f"generated_tokens{tag}.npy"), tokens)
+    np.save(os.path.join(out_dir, f"prompt_lens{tag}.npy"), np.asarray(res.prompt_lens, dtype=np.float32))
 
 
 def main(argv=None):
@@ -113,6 +146,15 @@ def main(argv=None):
                          # the GPU that owns it; insert + relevance exchanged over RCCL each batch)
                          index_group=groups.dp_group if groups.dp_size > 1 and not args.llm_only else None,
                          overlap_prefill=args.overlap_prefill == "on" and not args.no_overlap)
+    last_generation = []
+    if args.dump_outputs:
+        # every schedule ends a batch in LLMEngine.finish (generate calls it too): keep its last result
+        finish = pipe.engine.finish
+
+        def keep_last(*a, **kw):
+            last_generation[:] = [finish(*a, **kw)]
+            return last_generation[0]
+        pipe.engine.finish = keep_last
 
     # the latency half runs at every TP degree (the TP followers replay the continuous engine's steps)
     probe_steps = list(range(args.warmup + args.steps, args.warmup + args.steps + args.latency_steps)) \
@@ -150,6 +192,8 @@ def main(argv=None):
 
     # one report per DP replica: TP followers ran the same threads as their leader
     lead = groups.tp_rank == 0
+    if args.dump_outputs and lead and last_generation:
+        dump_outputs(args.dump_outputs, last_generation[0], rank, world)
     threads_local = sum(r.threads for r in results) if lead else 0
     lat_local = [x for r in results for x in r.latencies_s] if lead else []
     gen_tokens_local = sum(r.generated_tokens for r in results) if lead else 0

@@ -9,7 +9,7 @@ export MASTER_ADDR=127.0.0.1 MASTER_PORT=${MASTER_PORT:-29537} WORLD_SIZE=$DP CF
 pids=()
 for ((r = 0; r < DP; r++)); do
   RANK=$r LOCAL_RANK=$r timeout -s ABRT -k 10 ${DP_LIMIT:-300} python -u bench.py --gpus $DP --steps 2 --warmup 1 \
-    --threads-per-gpu 32 --max-new 64 ${BENCH_ARGS} \
+    --full --threads-per-gpu 32 --max-new 64 ${BENCH_ARGS} \
     > gpurun_out/dp_rehearsal_$r.out 2> gpurun_out/dp_rehearsal_$r.err &
   pids+=($!)
 done

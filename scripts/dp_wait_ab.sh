@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for mode in poll block; do
   CFC_NODE_MIN_ADMIT=1 CFC_NODE_ADMIT_WAIT_MS=50 CFC_DP_WAIT=$mode CFC_DIST_BACKEND=gloo timeout -k 10 520 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port 2953${#mode} bench.py --gpus 2 --pipeline node --steps 1 --warmup 1 \
-    --threads-per-gpu 64 --service-latency-rate 0.5 --service-latency-threads 12 \
+    --full --threads-per-gpu 64 --service-latency-rate 0.5 --service-latency-threads 12 \
     > gpurun_out/r06_dpwait_$mode.out 2> gpurun_out/r06_dpwait_$mode.err || { tail -5 gpurun_out/r06_dpwait_$mode.err; exit 1; }
   python - $mode <<'PY'
 import json, sys

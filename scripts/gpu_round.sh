@@ -1,5 +1,6 @@
 #!/bin/bash
-# One GPU session: build -> kernel numerics -> all GPU tests -> smoke -> full end-to-end bench.
+# One GPU session: build -> kernel numerics -> all GPU tests -> smoke -> end-to-end bench with the
+# script's arguments (pass --full for the latency and search probes after the timed steps).
 # Every GPU step has its own time limit; the chain stops at the first failure.
 set -o pipefail
 mkdir -p gpurun_out

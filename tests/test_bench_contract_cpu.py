@@ -1,7 +1,8 @@
 """The driver's bench.py contract, rehearsed on the CPU: one rank and two ranks under
 ``torch.distributed.run`` (gloo, 127.0.0.1), tiny random-init models.  Checks the single JSON line
 rank 0 prints (keys, whole-job aggregate value, n_gpus, weak-scaling batch, parallelism tag) so the
-multi-GPU path the driver runs at N = 2..8 is exercised by construction here."""
+multi-GPU path the driver runs at N = 2..8 is exercised by construction here.  The runs pass
+``--full`` (the probes after the timed window); one test checks the plain run and ``--dump-outputs``."""
 from __future__ import annotations
 
 import json
@@ -13,8 +14,10 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--model", "tiny", "--encoder", "tiny", "--threads-per-gpu", "2", "--max-new", "3", "--steps", "2",
-        "--warmup", "1", "--index-prefill", "0", "--prefill-tokens", "4096", "--service-latency-threads", "3"]
+PLAIN = ["--model", "tiny", "--encoder", "tiny", "--threads-per-gpu", "2", "--max-new", "3", "--steps", "2",
+         "--warmup", "1", "--index-prefill", "0", "--prefill-tokens", "4096"]
+# --full: the probes after the timed window (latency points, service light load, topic search)
+ARGS = [*PLAIN, "--full", "--service-latency-threads", "3"]
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
         "vs_baseline", "dtype", "data", "config"}
 
@@ -115,3 +118,25 @@ def test_bench_node_pipeline_dp_topology_two_ranks():
     assert sum(p["summaries"] for p in pr) == 2 * 2 * 3 + 3
     sl = d["latency_service_light"]
     assert sl["threads"] == 3 and 0 < sl["p50_s"] <= sl["p95_s"] and d["dp_wait"] == "block"
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full nothing runs after the timed window (every probe's entry is null); with
+    --dump-outputs the last timed step's generation is written as float32 arrays, and a second run
+    with the same arguments sees the same inputs and writes the same arrays."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, "bench.py", "--gpus", "1", *PLAIN, "--dump-outputs", str(tmp_path / name)])
+        _check(d, 1, latency=False)
+        for key in ("latency_mode", "latency_mode_light", "latency_service_light", "search_latency"):
+            assert d[key] is None, key
+        files = sorted(f.name for f in (tmp_path / name).iterdir())
+        assert files == ["generated_tokens.npy", "prompt_lens.npy"]
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in files})
+    a, b = runs
+    assert a["generated_tokens"].dtype == np.float32 and a["generated_tokens"].shape == (2, 3)
+    assert a["prompt_lens"].dtype == np.float32 and a["prompt_lens"].shape == (2,) and (a["prompt_lens"] > 1).all()
+    assert (a["generated_tokens"] >= 0).all()
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f

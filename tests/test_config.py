@@ -1,6 +1,6 @@
 """Schema-first configuration: env parsing and coercion, aliases, discriminant driver selection,
-secret-backed fields, the exported JSON schema -- and, when the reference checkout is mounted, a
-sweep asserting every service setting and driver field the reference declares
+secret-backed fields, the exported JSON schema -- and, over the reference's schema files stored under
+tests/golden/reference_schemas, a sweep asserting every service setting and driver field the reference declares
 (docs/schemas/configs/services/*.json, adapters/*.json, adapters/drivers/*/*.json) exists here
 with the same env var(s) and default, so an existing deployment's environment keeps working.
 Mirrors adapters/copilot_config/tests (test_runtime_loader.py, test_schema_validation.py)."""
@@ -16,8 +16,7 @@ from copilot_for_consensus_amd.config.loader import (ConfigError, config_json_sc
                                                      load_adapter_config)
 from copilot_for_consensus_amd.security.secrets import EnvSecretProvider
 
-REF = Path("/root/reference/docs/schemas/configs")
-needs_ref = pytest.mark.skipif(not REF.exists(), reason="reference checkout not mounted")
+REF = Path(__file__).parent / "golden" / "reference_schemas" / "configs"
 
 
 def test_defaults_without_env():
@@ -86,8 +85,7 @@ def _envs(e):
     return set(e) if isinstance(e, list) else {e}
 
 
-@needs_ref
-@pytest.mark.parametrize("path", sorted(p.name for p in (REF / "services").glob("*.json")) if REF.exists() else [])
+@pytest.mark.parametrize("path", sorted(p.name for p in (REF / "services").glob("*.json")))
 def test_service_settings_match_reference(path):
     ref = json.loads((REF / "services" / path).read_text())
     svc = ref["service_name"]
@@ -106,8 +104,7 @@ def test_service_settings_match_reference(path):
     assert diffs == [] and not missing_adapters, (diffs, missing_adapters)
 
 
-@needs_ref
-@pytest.mark.parametrize("path", sorted(p.name for p in (REF / "adapters").glob("*.json")) if REF.exists() else [])
+@pytest.mark.parametrize("path", sorted(p.name for p in (REF / "adapters").glob("*.json")))
 def test_adapter_drivers_match_reference(path):
     ref = json.loads((REF / "adapters" / path).read_text())
     adapter = path[:-5]

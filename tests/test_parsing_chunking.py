@@ -29,7 +29,7 @@ from copilot_for_consensus_amd.retry import (DocumentNotFoundError, RetryConfig,
                                              handle_event_with_retry, retry_with_backoff)
 
 FIX = Path(__file__).parent / "fixtures" / "sample.mbox"
-REF_MBOX = Path("/root/reference/tests/fixtures/mailbox_sample/test-archive.mbox")
+REF_MBOX = Path(__file__).parent / "golden" / "reference_mailbox" / "test-archive.mbox"
 
 
 def _msg(mid, body="hello world.", irt=None, frm="a@example.com", subject="Topic", date="Mon, 1 Jan 2024 10:00:00 +0000",
@@ -73,7 +73,6 @@ def test_parse_fixture_threads():
         assert t["first_message_date"] <= t["last_message_date"]
 
 
-@pytest.mark.skipif(not REF_MBOX.exists(), reason="reference checkout not mounted")
 def test_reference_fixture_threads():
     msgs, errs = MessageParser().parse_mbox_bytes(REF_MBOX.read_bytes(), "0123456789abcdef")
     assert errs == [] and len(msgs) == 10
