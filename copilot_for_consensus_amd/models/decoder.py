@@ -440,8 +440,9 @@ class DecoderModel:
         self.decode_gemm = mode
         # prefill GEMM (packed prompt rows): "hip" = the hand-written MFMA GEMM (csrc/kernels/pgemm.hip,
         # SwiGLU fused into gate/up, reading the packed weights), "lib" = the library GEMM + silu_mul
-        # (CFC_PREFILL_GEMM); CFC_PGEMM_VARIANT picks pgemm's K loop (CFC_PGEMM_VARIANT_SWIGLU the
-        # gate/up projection's, CFC_PGEMM_VARIANT when unset)
+        # (CFC_PREFILL_GEMM); CFC_PGEMM_VARIANT picks pgemm's kernel, one of K.PGEMM_VARIANTS
+        # (CFC_PGEMM_VARIANT_SWIGLU the gate/up projection's, CFC_PGEMM_VARIANT when unset); any
+        # other name, a retired variant's included, is an error here rather than another kernel
         pm = os.environ.get("CFC_PREFILL_GEMM", self.PREFILL_GEMM_DEFAULT)
         if pm not in ("hip", "lib"):
             raise ValueError(f"CFC_PREFILL_GEMM={pm!r}: expected hip or lib")

@@ -6,14 +6,36 @@
 // N, K = 384 .. 3072).  Compute bound: 256 x 256 output tile per workgroup, 128 FLOP per staged
 // byte, so each CU must keep ~55 GB/s of X and W arriving through L2 while its MFMAs run.
 //
-//   * workgroup = 8 waves (2 along M x 4 along N), 512 threads, one workgroup per CU (launch
-//     bound 1), each wave a 128 x 64 output block: 8 x 4 accumulator tiles of 16 x 16
-//     (v_mfma_f32_16x16x32_bf16, 128 accumulator VGPRs);
+// Three kernels are selected in production, picked by the variant code in cfc_pgemm's epi_v
+// (pgemm_launch); two more ("w4", "pps") lost their races and are reachable by name only:
+//
+//   code  name      kernel            runs when
+//   1     "stage2"  pgemm_kernel      row-major W.  Two 64-KB LDS stages, one barrier per K-tile.  The
+//                                     encoders' default: it wins at K <= 512 (MiniLM qkv + bias 442
+//                                     TF/s against 313 for the ping-pong kernel, whose pipeline six
+//                                     K-tiles are too short for; models/encoder.py, PGEMM_MAX_K).
+//   3     "pp"      pgemm_pp_kernel   either W layout, every epilogue.  Two wave groups ping-ponging
+//                                     over half-tile stages.  Also what code 1 runs for a packed W,
+//                                     what code 6 runs where "ppp" cannot, the only kernel with the
+//                                     fp32 epilogue, and the bit-identity oracle of "ppp" in the tests.
+//   6     "ppp"     pgemm_ppp_kernel  packed W, bf16 or SwiGLU epilogue, K >= 128: "pp" made
+//                                     persistent.  The decoder's default for all four projections.
+//   4     "w4"      pgemm_w4_kernel   nobody: four waves of 128 x 128, break-even at best
+//                                     (profiles/ROOFLINE.md, rounds 3-4).
+//   5     "pps"     pgemm_pp_kernel   nobody: "pp" with LDS-staged bf16 stores (STAGED), round 4's
+//                                     default until "ppp" brought its own staged epilogue.
+//
+// Any other code is hipErrorInvalidValue.  pgemm_ln_kernel (cfc_pgemm_ln) is the 2-stage K loop on
+// 128-row x 384-column tiles with the encoders' residual + LayerNorm as its epilogue.
+//
+// Common to all of them:
+//   * 256 x 256 output tile per workgroup of 8 waves (512 threads, launch bound 1: one workgroup
+//     per CU), each wave a 128 x 64 output block: 8 x 4 accumulator tiles of 16 x 16
+//     (v_mfma_f32_16x16x32_bf16, 128 accumulator VGPRs) -- "w4": 4 waves of 128 x 128;
 //   * K in 64-deep tiles, both operands staged global -> LDS by LDS-DMA (`global_load_lds_dwordx4`,
-//     written in asm: hipcc orders nothing behind it and never drains it before an ordinary load),
-//     two LDS stages of 64 KB: the DMA of tile t+1 runs under the MFMAs of tile t, one barrier per
-//     tile (its counted wait retires tile t's DMA and the previous tile's ds_reads together);
-//   * each LDS image is 256 rows x 128 B, XOR-swizzled through the SOURCE address (chunk c of row r
+//     written in asm: hipcc orders nothing behind it and never drains it before an ordinary load)
+//     under the MFMAs of the tile before, retired by counted waits in front of raw barriers;
+//   * row-major LDS images have 128-B rows, XOR-swizzled through the SOURCE address (chunk c of row r
 //     at r * 128 + ((c ^ (r & 7)) << 4)), so the 16-row ds_read_b128 fragment reads are
 //     bank-conflict free (guide rule 21 / T2) -- the same image as the decode GEMM's X stage;
 //   * operands swapped in the MFMA (W fragment as A, X fragment as B) so each lane's accumulator
@@ -23,7 +45,8 @@
 //     so the ~32 workgroups resident on one XCD share X rows and W rows in that XCD's L2.
 //
 // Epilogues: bf16; + bias (encoder qkv); + bias -> GELU(erf) (encoder FFN up); SwiGLU over 8-row
-// interleaved gate/up weights (decoder gate_up, reference.interleave_gate_up) -> [M, N/2].
+// interleaved gate/up weights (decoder gate_up, reference.interleave_gate_up) -> [M, N/2]; the fp32
+// accumulators (tensor-parallel partials).
 //
 // Bounds: K % 64 == 0, N % 64 == 0, ldo % 4 == 0; M and N need not be tile multiples (rows past
 // the edge read the last valid row, their results are never stored).  X, W byte spans < 4 GiB
@@ -170,6 +193,12 @@ __device__ __forceinline__ void pg_epilogue_staged(const f32x4_t (&acc)[8][4], u
   }
 }
 
+// ---- "stage2": two whole-tile LDS stages -------------------------------------------------------------
+// Wave (wr, wc) of 2 x 4 owns rows 128 wr .. +128, columns 64 wc .. +64.  Each stage holds one K-tile
+// of both operands (X image then W image, 256 rows x 128 B each, 64 KB); the DMA of tile t+1 runs
+// under the MFMAs of tile t, one barrier per tile (its wait retires tile t's DMA and the previous
+// tile's ds_reads together).  Nothing covers that wait, which is what "pp" removes on long K; at
+// K <= 512 this kernel's short prologue wins (file header).
 template <int EPI>
 __global__ void __launch_bounds__(512, 1)
     pgemm_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W, const uint16_t* __restrict__ bias,
@@ -246,148 +275,7 @@ __global__ void __launch_bounds__(512, 1)
 }
 
 
-// ---- v2: BK = 32 ring of R LDS slots ------------------------------------------------------------
-// Same tile, waves and epilogue as pgemm_kernel; the K loop is a ring instead of a 2-stage double
-// buffer.  A slot is one 32-deep K step of both operands: A image then B image, 256 rows x 64 B
-// each (32 KB).  Step t's MFMAs run on fragments read from LDS during step t - 1, so the LDS reads
-// of step t + 1 overlap them.  At the top of step t each wave waits (counted vmcnt) for ITS DMA of
-// step t + 1 with the later steps left in flight and retires its ds_reads of step t (lgkmcnt(0));
-// then one raw barrier: step t + 1 is readable everywhere and step t's slot (in registers in every
-// wave) is free, so the DMA of step t + R goes into it right away.  A slot's DMA thus has R - 1
-// steps of MFMA work (~1k cycles per step per SIMD pair) to land, against one 64-deep tile in the
-// 2-stage kernel: what that kernel waits for at its vmcnt(0) (guide "Pipelining across barriers").
-//
-// 64-B image rows: 4 rows share a 256-B bank row, so the 16-row fragment read (lane: row
-// lane & 15, chunk lane >> 4) is swizzled as chunk' = chunk ^ f((row >> 2) & 3), f = 0,3,2,1: every
-// ds_read_b128 lane group then covers the 16 bank slots of one bank row exactly once.  The DMA
-// writes lane-linear (16-row x 64-B piece per wave instruction), so the swizzle goes on its source
-// chunk (guide rule 21).
-constexpr int PR_BK = 32;
-constexpr int PR_SLOT = (PG_BM + PG_BN) * PR_BK * 2;   // 32 KB
-
-__device__ __forceinline__ int pr_f(int x) { return (4 - x) & 3; }
-
-template <int EPI, int R>
-__global__ void __launch_bounds__(512, 1)
-    pgemm_ring_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W,
-                      const uint16_t* __restrict__ bias, uint16_t* __restrict__ out, int M, int N, int K, int ldo,
-                      int tiles_m, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) char smem[R * PR_SLOT];
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wr = w >> 2, wc = w & 3;
-
-  const int nwg = tiles_m * tiles_n;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int per_group = PG_GROUP_M * tiles_n;
-  const int first_m = (id / per_group) * PG_GROUP_M;
-  const int gsz = min(tiles_m - first_m, PG_GROUP_M);
-  const int in_group = id % per_group;
-  const int m0 = (first_m + in_group % gsz) * PG_BM;
-  const int n0 = (in_group / gsz) * PG_BN;
-
-  // ---- DMA: wave w moves pieces w and w + 8 of A (image rows 16 p .. 16 p + 15) and of B;
-  // lane l lands at row l >> 2, slot chunk l & 3 of its piece
-  const int prow = lane >> 2, pch = (lane & 3) ^ pr_f((prow >> 2) & 3);
-  uint32_t va[2], vb[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = 16 * (w + 8 * i) + prow;
-    va[i] = ((uint32_t)min(m0 + r, M - 1) * (uint32_t)K + 8u * pch) * 2u;
-    vb[i] = ((uint32_t)min(n0 + r, N - 1) * (uint32_t)K + 8u * pch) * 2u;
-  }
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(pg_lds_t*)smem + w * 1024);
-  auto issue = [&](int t, int s) {
-    const uint16_t* xa = X + (size_t)t * PR_BK;
-    const uint16_t* wb = W + (size_t)t * PR_BK;
-    const uint32_t la = lds0 + s * PR_SLOT;
-    pg_glds16(va[0], xa, la);
-    pg_glds16(va[1], xa, la + 8192);
-    pg_glds16(vb[0], wb, la + PG_BM * 64);
-    pg_glds16(vb[1], wb, la + PG_BM * 64 + 8192);
-  };
-
-  f32x4_t acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int frow = (lane & 15) * 64;
-  const int ch = ((lane >> 4) ^ pr_f(((lane & 15) >> 2) & 3)) << 4;
-  const char* ra = smem + wr * 128 * 64 + frow + ch;
-  const char* rb = smem + PG_BM * 64 + wc * 64 * 64 + frow + ch;
-  const int nk = K / PR_BK;
-  // Fragments of step t are read from LDS during step t - 1's MFMAs.  B (4 fragments) is
-  // double-buffered and read first; A fragment i is re-read in place right after its last MFMA of
-  // the step (sched_barrier pins each read there: hoisted, the reads would double the live
-  // fragments and spill).  The reads of the last step's "next" fragments touch a slot nobody
-  // writes any more and are never used (branch-free MFMA stream).
-  bf16x8_t af[8], bq[2][4];
-  auto rd_a = [&](int s, int i) { return *reinterpret_cast<const bf16x8_t*>(ra + s * PR_SLOT + i * 16 * 64); };
-  auto rd_b = [&](int s, int j) { return *reinterpret_cast<const bf16x8_t*>(rb + s * PR_SLOT + j * 16 * 64); };
-  // Wait (own DMAs) for step t + 1 with the steps after it left in flight, retire this wave's
-  // ds_reads, then the barrier: step t + 1 readable everywhere, slot of step t free.
-  auto sync_next = [&](int t) {
-    const int ahead = min(nk - 2 - t, R - 2);
-    if (ahead >= 3)
-      asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else if (ahead == 2)
-      asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else if (ahead == 1)
-      asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  };
-#define PR_STEP(T, S, S1, BC, BN)                                                                         \
-  do {                                                                                                   \
-    if ((T) + 1 < nk) {                                                                                  \
-      sync_next(T);                                                                                      \
-      if ((T) + R < nk) issue((T) + R, S);                                                               \
-    }                                                                                                    \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) BN[j] = rd_b(S1, j);                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-    __builtin_amdgcn_s_setprio(1);                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                      \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] =                                          \
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(BC[j], af[i], acc[i][j], 0, 0, 0);                     \
-      af[i] = rd_a(S1, i);                                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                                 \
-    }                                                                                                    \
-    __builtin_amdgcn_s_setprio(0);                                                                       \
-  } while (0)
-  for (int t = 0; t < R && t < nk; ++t) issue(t, t);
-  {
-    const int ahead = min(nk - 1, R - 1);   // step 0 landed, steps 1 .. ahead in flight
-    if (ahead >= 4)
-      asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
-    else if (ahead == 3)
-      asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
-    else if (ahead == 2)
-      asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-    else if (ahead == 1)
-      asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) bq[0][j] = rd_b(0, j);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) af[i] = rd_a(0, i);
-  int s = 0;   // ring slot of step t
-  for (int t = 0; t < nk; t += 2) {
-    const int s1 = (s == R - 1) ? 0 : s + 1;
-    const int s2 = (s1 == R - 1) ? 0 : s1 + 1;
-    PR_STEP(t, s, s1, bq[0], bq[1]);
-    PR_STEP(t + 1, s1, s2, bq[1], bq[0]);   // nk is even (K % 64 == 0)
-    s = s2;
-  }
-#undef PR_STEP
-  pg_epilogue<EPI>(acc, bias, out, M, N, ldo, m0 + wr * 128, n0 + wc * 64);
-}
-
-
-// ---- v3: ping-pong of two wave groups over half-tile LDS-DMA stages ------------------------------
+// ---- "pp": ping-pong of two wave groups over half-tile LDS-DMA stages ----------------------------
 // The 2-stage kernel above waits 30-35 % of its cycles (profiles/r03s2_pmc_pgemm_vs_hipblaslt.txt):
 // every wave reaches the tile's vmcnt(0) + barrier at once, then all read LDS at once, and nothing
 // covers either.  Here the 8 waves are two groups of 4 (waves 0-3, 4-7: one of each on every SIMD),
@@ -400,10 +288,10 @@ __global__ void __launch_bounds__(512, 1)
 //     W0 = W rows 0-127, W1 = W rows 128-255; two K-tile buffers = 128 KB of LDS;
 //   * K-tile kt runs in two segments of 32 MFMAs per wave: A (X0 and both W halves: the wave's first
 //     64 rows) and B (X1: its last 64 rows, W fragments kept in registers);
-//   * stream of half-tiles: segment A of tile kt issues tile kt+1's {W1, X1}, segment B issues tile
-//     kt+2's {X0, W0} -- each into a half whose last reader (either group) retired its ds_reads
-//     (lgkmcnt(0)) before the barrier that precedes the issue; counted vmcnt(8) / vmcnt(6) leave
-//     2-3 half-tiles of DMA in flight per wave (48-64 KB per CU) and retire exactly what the next
+//   * stream of half-tiles: segment A of tile kt issues tile kt+1's X1, segment B issues tile
+//     kt+2's {X0, W0, W1} -- each into a half whose last reader (either group) retired its ds_reads
+//     (lgkmcnt(0)) before the barrier that precedes the issue; the counted vmcnt(8) of both segments
+//     leaves 4 half-tiles of DMA in flight per wave (64 KB per CU) and retires exactly what the next
 //     segment reads, one barrier (two for the lagging group) ahead of the read;
 //   * X image: 128 rows x 128 B per half, chunk c of image row r at r*128 + ((c ^ (r & 7)) << 4)
 //     (swizzled through the DMA SOURCE address, guide rule 21), 8-row x 128-B pieces;
@@ -421,13 +309,11 @@ __device__ __forceinline__ void pp_wait_barrier() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
 }
 
-// PF: probe flags (scripts/bench_pgemm.py --probe; 0 in production): 1 = no s_setprio, 2 = static
-// priority 1 for group 1 instead of per-segment flips.  gm = M-tiles per N sweep of the tile order.
-template <int EPI, bool PACKED, int PF = 0>
+// STAGED ("pps"): the bf16 outputs leave through LDS as whole row segments (pg_epilogue_staged).
+template <int EPI, bool PACKED, bool STAGED = false>
 __global__ void __launch_bounds__(512, 1)
     pgemm_pp_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W, const uint16_t* __restrict__ bias,
-                    uint16_t* __restrict__ out, int M, int N, int K, int ldo, int tiles_m, int tiles_n, int wnw,
-                    int gm = PG_GROUP_M) {
+                    uint16_t* __restrict__ out, int M, int N, int K, int ldo, int tiles_m, int tiles_n, int wnw) {
   __shared__ __attribute__((aligned(16))) char smem[2 * PP_BUF];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -435,9 +321,9 @@ __global__ void __launch_bounds__(512, 1)
 
   const int nwg = tiles_m * tiles_n;
   const int id = xcd_remap(blockIdx.x, nwg);
-  const int per_group = gm * tiles_n;
-  const int first_m = (id / per_group) * gm;
-  const int gsz = min(tiles_m - first_m, gm);
+  const int per_group = PG_GROUP_M * tiles_n;
+  const int first_m = (id / per_group) * PG_GROUP_M;
+  const int gsz = min(tiles_m - first_m, PG_GROUP_M);
   const int in_group = id % per_group;
   const int m0 = (first_m + in_group % gsz) * PG_BM;
   const int n0 = (in_group / gsz) * PG_BN;
@@ -514,11 +400,14 @@ __global__ void __launch_bounds__(512, 1)
     }
   };
 
-  // W1E (PF & 32): tile kt+2's W1 half is issued with its X0 / W0 in segment B of tile kt (its slot is
-  // free once both groups' segment-A reads of tile kt retired) instead of in segment A of tile kt+1,
-  // so every half has ~2 segments between its issue and the wait that retires it (was 1 for W1).
-  constexpr bool W1E = (PF & 32) != 0;
-  // ---- prologue: tile 0 whole, tile 1's {X0, W0} (+ W1); tile 0's X0 / W0 / W1 landed in every wave
+  // Two measured choices are fixed in this schedule: no s_setprio around the MFMA segments (1.5-2.5 %
+  // faster than per-segment priority flips on all four headline shapes,
+  // profiles/r04_pgemm_pp_probes.jsonl pf1 vs pf0), and tile kt+2's W1 half issued early, with its
+  // X0 / W0 in segment B of tile kt (its slot is free once both groups' segment-A reads of tile kt
+  // retired) rather than in segment A of tile kt+1, so every half has ~2 segments between its
+  // issue and the wait that retires it (+0.6-1.7 %: qkv 580 -> 571 us, o 384 -> 378, gate_up 2665
+  // -> 2631, down 1311 -> 1299; profiles/r04_pgemm_w1e.jsonl).
+  // ---- prologue: tile 0 whole, tile 1's {X0, W0, W1}; tile 0's X0 / W0 / W1 landed in every wave
   issue_x(0, 0);
   issue_w(0, 0);
   issue_w(0, 1);
@@ -526,134 +415,79 @@ __global__ void __launch_bounds__(512, 1)
   if (nk > 1) {
     issue_x(1, 0);
     issue_w(1, 0);
-    if constexpr (W1E) {
-      issue_w(1, 1);
-      pp_wait_barrier<8>();
-    } else {
-      pp_wait_barrier<6>();
-    }
+    issue_w(1, 1);
+    pp_wait_barrier<8>();
   } else {
     pp_wait_barrier<2>();
   }
   if (grp == 1) pp_barrier();   // the stagger: group 1 runs one barrier behind group 0
-  if constexpr ((PF & 2) != 0) {
-    if (grp == 1) __builtin_amdgcn_s_setprio(1);
-  }
-  constexpr bool FLIP = (PF & 3) == 0;
 
-  // ablation probes (never in production): 4 = no LDS-DMA in the loop, 8 = no fragment ds_reads
-  // (fragments of tile 0 reused, kept live), 16 = no MFMA (fragments kept live)
-  constexpr bool DMA = (PF & 4) == 0, RD = (PF & 8) == 0, MM = (PF & 16) == 0;
   bf16x8_t wf[4][2], xf[4][2];
-  if constexpr (!RD) {
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = (kt & 1) * PP_BUF;
+    // ======== segment A: load part (tile kt+1's X1 into the other buffer; fragments)
+    if (kt + 1 < nk) issue_x(kt + 1, 1);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) wf[j][kk] = rd_w(0, j, kk);
+      for (int kk = 0; kk < 2; ++kk) wf[j][kk] = rd_w(buf, j, kk);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) xf[i][kk] = rd_x(0, 0, i, kk);
-  }
-  auto keep = [&]() {
+      for (int kk = 0; kk < 2; ++kk) xf[i][kk] = rd_x(buf, 0, i, kk);
+    // retire tile kt's X1 (segment B reads it) and this wave's ds_reads
+    if (kt + 1 < nk) pp_wait_barrier<8>();
+    else pp_wait_barrier<0>();
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) asm volatile("" : "+v"(wf[j][kk]), "+v"(xf[j][kk]));
-  };
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = (kt & 1) * PP_BUF;
-    // ======== segment A: load part (tile kt+1's W1 / X1 into the other buffer; fragments)
-    if (DMA && kt + 1 < nk) {
-      if constexpr (!W1E) issue_w(kt + 1, 1);
-      issue_x(kt + 1, 1);
-    }
-    if constexpr (RD) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) wf[j][kk] = rd_w(buf, j, kk);
+    for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) xf[i][kk] = rd_x(buf, 0, i, kk);
-    } else {
-      keep();
-    }
-    // retire tile kt's X1 (segment B reads it) and this wave's ds_reads
-    if (DMA && kt + 1 < nk) pp_wait_barrier<8>();
-    else pp_wait_barrier<0>();
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (FLIP) __builtin_amdgcn_s_setprio(1);
-    if constexpr (MM) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][kk], xf[i][kk], acc[i][j], 0, 0, 0);
-    } else {
-      keep();
-    }
-    if constexpr (FLIP) __builtin_amdgcn_s_setprio(0);
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][kk], xf[i][kk], acc[i][j], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     pp_barrier();
-    // ======== segment B: load part (tile kt+2's X0 / W0 into this buffer's free halves)
-    if (DMA && kt + 2 < nk) {
+    // ======== segment B: load part (tile kt+2's X0 / W0 / W1 into this buffer's free halves)
+    if (kt + 2 < nk) {
       issue_x(kt + 2, 0);
       issue_w(kt + 2, 0);
-      if constexpr (W1E) issue_w(kt + 2, 1);
+      issue_w(kt + 2, 1);
     }
-    if constexpr (RD) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) xf[i][kk] = rd_x(buf, 1, i, kk);
+    // retire tile kt+1's X0 / W0 / W1 (next segment A reads them)
+    if (kt + 2 < nk) pp_wait_barrier<8>();
+    else if (kt + 1 < nk) pp_wait_barrier<2>();
+    else pp_wait_barrier<0>();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) xf[i][kk] = rd_x(buf, 1, i, kk);
-    } else {
-      keep();
-    }
-    // retire tile kt+1's X0 / W0 / W1 (next segment A reads them)
-    if (DMA && kt + 2 < nk) pp_wait_barrier<W1E ? 8 : 6>();
-    else if (DMA && kt + 1 < nk) pp_wait_barrier<2>();
-    else pp_wait_barrier<0>();
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (FLIP) __builtin_amdgcn_s_setprio(1);
-    if constexpr (MM) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][kk], xf[i][kk], acc[4 + i][j], 0, 0, 0);
-    } else {
-      keep();
-    }
-    if constexpr (FLIP) __builtin_amdgcn_s_setprio(0);
+        for (int j = 0; j < 4; ++j)
+          acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][kk], xf[i][kk], acc[4 + i][j], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     pp_barrier();
-  }
-  if constexpr (!MM) {      // the ablation's outputs depend on its fragments (nothing is dead code)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[0][j] += __builtin_bit_cast(f32x4_t, wf[j][0]) + __builtin_bit_cast(f32x4_t, xf[j][1]);
   }
 
   // wave rows: segment A's m-tiles i = tile rows 128 grp + 16 i, segment B's = 128 grp + 64 + 16 i.
-  // STG (PF & 64): the bf16 / SwiGLU outputs leave through LDS as whole row segments.  After this
-  // wave's last barrier of the loop no wave reads LDS any more (the lagging group's last reads were
-  // retired before it) and every DMA landed, so each wave may use its own 16-KB slice.
-  // staged stores for the bf16 epilogue; SwiGLU (half the columns, 8-byte pieces) measured 0.7 %
-  // faster with the direct stores once its math was spread over both lane halves
-  constexpr bool STG = (PF & 64) != 0 && EPI == PG_BF16;
-  if constexpr (STG)
+  // STAGED: after this wave's last barrier of the loop no wave reads LDS any more (the lagging
+  // group's last reads were retired before it) and every DMA landed, so each wave may use its own
+  // 16-KB slice.  Staged stores for the bf16 epilogue only; SwiGLU (half the columns, 8-byte pieces)
+  // measured 0.7 % faster with the direct stores once its math was spread over both lane halves
+  static_assert(!STAGED || EPI == PG_BF16, "staged stores: bf16 epilogue only");
+  if constexpr (STAGED)
     pg_epilogue_staged<EPI>(acc, out, M, N, ldo, m0 + grp * 128, n0 + wc * 64, smem + w * 16384);
   else
     pg_epilogue<EPI>(acc, bias, out, M, N, ldo, m0 + grp * 128, n0 + wc * 64);
   if (grp == 0) pp_barrier();   // matches group 1's stagger barrier
 }
 
-// ---- v4: the ping-pong kernel made persistent (packed W; bf16 and SwiGLU epilogues) ----------------
+// ---- "ppp": the ping-pong kernel made persistent (packed W; bf16 and SwiGLU epilogues) ------------
 // Fitting t = a + b K over K = 1k..8k at M = 16384 (scripts/probe_pgemm_k.py, profiles/
 // r06_pgemm_k.jsonl) puts a fixed ~7 us (qkv) to ~16-20 us (gate_up) on every wave of 256 tiles:
 // each new workgroup starts with an idle prologue (its first two K-tiles' DMA round trip, every CU
@@ -1106,7 +940,7 @@ __global__ void __launch_bounds__(512, 1)
   }
 }
 
-// ---- v4: four waves of 128 x 128, one per SIMD, software-pipelined -----------------------------
+// ---- "w4": four waves of 128 x 128, one per SIMD, software-pipelined ---------------------------
 // The library's shape of the same tile (hipBLASLt MT256x256x64, 4 waves: profiles/
 // r03s2_pmc_pgemm_vs_hipblaslt.txt): a wave owns a 128 x 128 output block (64 accumulator tiles,
 // 256 registers -- the AGPR half of the file), so each MFMA costs half the LDS fragment bytes of the
@@ -1122,8 +956,12 @@ __global__ void __launch_bounds__(512, 1)
 //   * one barrier per step, behind a counted vmcnt (step t + 1's DMA; t + 2, t + 3 stay in flight)
 //     and lgkmcnt(0) (step t + 1's fragments in registers, every read of stage t % 4 retired).
 // X image: 64-B rows (16-row x 64-B DMA pieces), chunk c of row r at r*64 + ((c ^ f((r >> 2) & 3)) << 4),
-// f = 0,3,2,1: conflict-free 16-row fragment reads (the ring kernel's image).  W: packed fragments
-// (1 KB each, lane order) or a row-major image like X.
+// f = 0,3,2,1 (pr_f): 4 rows share a 256-B bank row, and with that swizzle every ds_read_b128 lane
+// group of the 16-row fragment read (lane: row lane & 15, chunk lane >> 4) covers the 16 bank slots
+// of one bank row exactly once.  The DMA writes lane-linear, so the swizzle goes on its source chunk
+// (guide rule 21).  W: packed fragments (1 KB each, lane order) or a row-major image like X.
+__device__ __forceinline__ int pr_f(int x) { return (4 - x) & 3; }
+
 constexpr int W4_BK = 32;
 constexpr int W4_STAGE = (PG_BM + PG_BN) * W4_BK * 2;   // 32 KB
 constexpr int W4_NS = 4;
@@ -1244,12 +1082,6 @@ __global__ void __launch_bounds__(256, 1)
   pg_epilogue<EPI>(acc, bias, out, M, N, ldo, m0 + wr * 128, n0 + wc * 128);
 }
 
-// production probe flags of the ping-pong kernel: no s_setprio (measured 1.5-2.5 % faster than the
-// per-segment flips on all four headline shapes, profiles/r04_pgemm_pp_probes.jsonl pf1 vs pf0) and
-// W1-early (+0.6-1.7 %: qkv 580 -> 571 us, o 384 -> 378, gate_up 2665 -> 2631, down 1311 -> 1299;
-// profiles/r04_pgemm_w1e.jsonl)
-constexpr int PP_PF = 1 | 32;
-
 // compute units of the current device (the persistent kernel's grid), looked up once per device
 // (relaxed atomics: concurrent first calls store the same value)
 int pg_cus() {
@@ -1290,30 +1122,32 @@ int pgemm_launch(const void* x, const void* w, const void* bias, void* out, int 
   const int tm = (M + PG_BM - 1) / PG_BM, tn = (N + PG_BN - 1) / PG_BN;
   const uint16_t *xp = (const uint16_t*)x, *wp = (const uint16_t*)w, *bp = (const uint16_t*)bias;
   uint16_t* op = (uint16_t*)out;
-  if (wnw > 0) {   // fragment-packed W: the ping-pong (default) or the 4-wave kernel
-    if (variant == 4) pgemm_w4_kernel<EPI, true><<<tm * tn, 256, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, wnw);
-    else if (variant == 5)   // LDS-staged bf16 / SwiGLU epilogue
-      pgemm_pp_kernel<EPI, true, PP_PF | 64><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, wnw);
-    else if (variant == 6) {   // persistent: one workgroup per CU walking the tiles
-      // (bias epilogues and K < 128 take the non-persistent kernel)
-      if constexpr (EPI == PG_BF16 || EPI == PG_SWIGLU) {
-        if (K >= 2 * PG_BK) return ppp_launch<EPI>(xp, wp, op, M, N, K, ldo, wnw, ppp_group_m(tn, K), PPP_STG, stream);
-      }
-      pgemm_pp_kernel<EPI, true, PP_PF><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, wnw);
-    }
-    else pgemm_pp_kernel<EPI, true, PP_PF><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, wnw);
+  const bool packed = wnw > 0;
+  if (variant != 1 && (variant < 3 || variant > 6)) return (int)hipErrorInvalidValue;
+  if (variant == 1 && !packed) {   // "stage2" reads a row-major W only
+    pgemm_kernel<EPI><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn);
     return (int)hipGetLastError();
   }
-  switch (variant) {
-    case 0: pgemm_ring_kernel<EPI, 5><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn); break;
-    case 1: pgemm_kernel<EPI><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn); break;
-    case 2: pgemm_ring_kernel<EPI, 4><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn); break;
-    case 3: pgemm_pp_kernel<EPI, false, PP_PF><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, 1); break;
-    case 4: pgemm_w4_kernel<EPI, false><<<tm * tn, 256, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, 1); break;
-    case 5: pgemm_pp_kernel<EPI, false, PP_PF | 64><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, 1); break;
-    case 6: pgemm_pp_kernel<EPI, false, PP_PF><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, 1); break;
-    default: return (int)hipErrorInvalidValue;
+  if (variant == 4) {   // "w4"
+    if (packed) pgemm_w4_kernel<EPI, true><<<tm * tn, 256, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, wnw);
+    else pgemm_w4_kernel<EPI, false><<<tm * tn, 256, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, 1);
+    return (int)hipGetLastError();
   }
+  if constexpr (EPI == PG_BF16) {   // "pps": staged stores for bf16 only, plain "pp" otherwise
+    if (variant == 5) {
+      if (packed) pgemm_pp_kernel<EPI, true, true><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, wnw);
+      else pgemm_pp_kernel<EPI, false, true><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, 1);
+      return (int)hipGetLastError();
+    }
+  }
+  if (variant == 6 && packed) {   // "ppp": no bias epilogues, and its prologue needs two K-tiles
+    if constexpr (EPI == PG_BF16 || EPI == PG_SWIGLU) {
+      if (K >= 2 * PG_BK) return ppp_launch<EPI>(xp, wp, op, M, N, K, ldo, wnw, ppp_group_m(tn, K), PPP_STG, stream);
+    }
+  }
+  // "pp", and whatever the ones above do not take
+  if (packed) pgemm_pp_kernel<EPI, true><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, wnw);
+  else pgemm_pp_kernel<EPI, false><<<tm * tn, 512, 0, stream>>>(xp, wp, bp, op, M, N, K, ldo, tm, tn, 1);
   return (int)hipGetLastError();
 }
 
@@ -1323,19 +1157,23 @@ int pgemm_launch_f32(const void* x, const void* w, void* out, int M, int N, int 
   const int tm = (M + PG_BM - 1) / PG_BM, tn = (N + PG_BN - 1) / PG_BN;
   const uint16_t *xp = (const uint16_t*)x, *wp = (const uint16_t*)w;
   uint16_t* op = (uint16_t*)out;
-  if (wnw > 0) pgemm_pp_kernel<PG_F32, true, PP_PF><<<tm * tn, 512, 0, stream>>>(xp, wp, nullptr, op, M, N, K, ldo, tm, tn, wnw);
-  else pgemm_pp_kernel<PG_F32, false, PP_PF><<<tm * tn, 512, 0, stream>>>(xp, wp, nullptr, op, M, N, K, ldo, tm, tn, 1);
+  if (wnw > 0) pgemm_pp_kernel<PG_F32, true><<<tm * tn, 512, 0, stream>>>(xp, wp, nullptr, op, M, N, K, ldo, tm, tn, wnw);
+  else pgemm_pp_kernel<PG_F32, false><<<tm * tn, 512, 0, stream>>>(xp, wp, nullptr, op, M, N, K, ldo, tm, tn, 1);
   return (int)hipGetLastError();
 }
 
 }  // namespace
 
-// epi & 15: 0 bf16, 1 + bias, 2 + bias -> GELU, 3 SwiGLU (out [M, N/2]); epi >> 4: K-loop variant
-// for a row-major W (0 BK = 32 ring of 5 slots, 1 the 2-stage BK = 64 kernel, 2 ring of 4 slots,
-// 3 the ping-pong kernel, 5 the same with the LDS-staged bf16 / SwiGLU epilogue, 6 the persistent
-// ping-pong kernel for a packed W -- the ping-pong kernel otherwise); ldo = output row stride.  wnw > 0: W is in the decode GEMM's
-// fragment-packed layout for bn = 16 wnw (cfc_dgemm_pack; N % (16 wnw) == 0) and runs on the
-// ping-pong kernel whatever the variant.
+// epi_v & 15, the epilogue: 0 bf16, 1 + bias, 2 + bias -> GELU, 3 SwiGLU (out [M, N/2]), 4 the fp32
+// accumulators (out is float, ldo in floats; always the ping-pong kernel).  epi_v >> 4, the kernel:
+//   1  the 2-stage kernel for a row-major W; the ping-pong kernel for a packed W;
+//   3  the ping-pong kernel;
+//   4  the 4-wave 128 x 128 kernel;
+//   5  the ping-pong kernel with LDS-staged stores for epilogue 0 (as 3 for the other epilogues);
+//   6  the persistent ping-pong kernel for a packed W, epilogue 0 or 3 and K >= 128; the ping-pong
+//      kernel otherwise;
+// and any other value is hipErrorInvalidValue.  ldo = output row stride.  wnw > 0: W is in the decode
+// GEMM's fragment-packed layout for bn = 16 wnw (cfc_dgemm_pack; N % (16 wnw) == 0), else row-major.
 CFC_API int cfc_pgemm(const void* x, const void* w, const void* bias, void* out, int M, int N, int K, int epi_v,
                       int ldo, int wnw, hipStream_t stream) {
   const int epi = epi_v & 15, variant = epi_v >> 4;
@@ -1351,32 +1189,6 @@ CFC_API int cfc_pgemm(const void* x, const void* w, const void* bias, void* out,
     case 4: return pgemm_launch_f32(x, w, out, M, N, K, ldo, wnw, stream);
     default: return (int)hipErrorInvalidValue;
   }
-}
-
-// Timing probe only (scripts/bench_pgemm.py --probe): the ping-pong kernel, bf16 epilogue, packed W
-// (wnw > 0), probe flags pf (see pgemm_pp_kernel) and tile-order group gm.
-CFC_API int cfc_pgemm_probe(const void* x, const void* w, void* out, int M, int N, int K, int wnw, int pf, int gm,
-                            hipStream_t stream) {
-  if (M < 1 || K % 64 || N % 64 || wnw < 1 || N % (16 * wnw) || gm < 1) return (int)hipErrorInvalidValue;
-  const int tm = (M + PG_BM - 1) / PG_BM, tn = (N + PG_BN - 1) / PG_BN;
-  const uint16_t *xp = (const uint16_t*)x, *wp = (const uint16_t*)w;
-  uint16_t* op = (uint16_t*)out;
-#define PP_PROBE(F) pgemm_pp_kernel<PG_BF16, true, F><<<tm * tn, 512, 0, stream>>>(xp, wp, nullptr, op, M, N, K, N, tm, tn, wnw, gm); break;
-  switch (pf) {
-    case 0: PP_PROBE(0)
-    case 1: PP_PROBE(1)
-    case 2: PP_PROBE(2)
-    case 5: PP_PROBE(5)
-    case 9: PP_PROBE(9)
-    case 13: PP_PROBE(13)
-    case 17: PP_PROBE(17)
-    case 21: PP_PROBE(21)
-    case 33: PP_PROBE(33)
-    case 97: PP_PROBE(97)
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef PP_PROBE
-  return (int)hipGetLastError();
 }
 
 // Timing probe only (scripts/probe_ppp_gm.py): the persistent kernel (packed W, bf16 or SwiGLU

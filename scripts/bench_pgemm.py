@@ -71,7 +71,7 @@ def main():
     ap.add_argument("--m", type=int, default=None, help="override M")
     ap.add_argument("--out", default="gpurun_out/pgemm.jsonl")
     ap.add_argument("--variants", nargs="*", default=["stage2", "pp", "packed"],
-                    help="row-major K loops (stage2 / ring5 / ring4 / pp / w4) and 'packed' / 'packed_w4' = "
+                    help="row-major K loops (stage2 / pp / w4) and 'packed' / 'packed_w4' = "
                          "the ping-pong / 4-wave kernel on the decode GEMM's fragment-packed weight")
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()

@@ -15,7 +15,7 @@ if __name__ == "__main__":
     M, N, Kd = int(os.environ.get("PMC_M", 16384)), 28672, 4096
     x = (torch.rand(M, Kd, device="cuda") * 2 - 1).bfloat16()
     w = ((torch.rand(N, Kd, device="cuda") * 2 - 1) / Kd ** 0.5).bfloat16()
-    for v in ("ring5", "stage2"):
+    for v in ("stage2", "pp"):
         for _ in range(3):
             K.pgemm(x, w, "bf16", variant=v)
     for _ in range(3):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Dispatches for rocprofv3 PMC passes of the prefill GEMM at the headline's qkv and gate_up shapes
-(16k rows, random operands): the persistent kernel ("ppp"), the one-tile ping-pong kernel ("pps")
+(16k rows, random operands): the persistent kernel ("ppp"), the one-tile ping-pong kernel ("pp")
 and the library GEMM (F.linear on a row-major copy), three dispatches each."""
 import os
 import sys
@@ -17,7 +17,7 @@ if __name__ == "__main__":
         x = (torch.rand(M, Kd, device="cuda") * 2 - 1).bfloat16()
         w = ((torch.rand(N, Kd, device="cuda") * 2 - 1) / Kd ** 0.5).bfloat16()
         pw = K.pack_dgemm_weight(w, swiglu=epi == "swiglu")
-        for v in ("ppp", "pps"):
+        for v in ("ppp", "pp"):
             for _ in range(3):
                 K.pgemm(x, pw, epi, variant=v)
         for _ in range(3):

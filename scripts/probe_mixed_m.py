@@ -6,7 +6,7 @@ For every Mistral-7B projection (packed weights, rotated over enough copies that
 its weight from HBM, as a decode step does) this times, in hipGraphs interleaved over rounds in one
 process (guide §5.4 rule 24):
   dg<M>   the decode GEMM (dgemm.hip) with the decoder's split / epilogue choice,
-  pg<M>   the prefill GEMM (pgemm.hip, "pps"),
+  pg<M>   the prefill GEMM (pgemm.hip, "ppp"),
   lib<M>  the library GEMM on a row-major copy (reference for what the chip does at that M).
 One JSON line per (shape, kernel, M) to gpurun_out/mixed_m.jsonl.
 """
@@ -78,7 +78,7 @@ def main():
                 else:
                     fns[("dg", M)] = [lambda p=p, x=x, s=split: K.dgemm(x, p, "part", s) for p in pws]
             if "pg" in args.kernels and M >= 256:
-                fns[("pg", M)] = [lambda p=p, x=x: K.pgemm(x, p, epi, variant="pps") for p in pws]
+                fns[("pg", M)] = [lambda p=p, x=x: K.pgemm(x, p, epi, variant="ppp") for p in pws]
             if "lib" in args.kernels:
                 if epi == "swiglu":
                     fns[("lib", M)] = [lambda w=w, x=x: K.silu_mul(F.linear(x, w), interleaved=True) for w in ws]

@@ -3,7 +3,7 @@
 and fit t = a + b * K -- the intercept a is what every workgroup's prologue (first DMA round trip),
 epilogue (store tail) and the launch cost per dispatch, the slope the K loop.  Random operands,
 hipGraph timing, interleaved rounds.  One JSON line per (shape, variant, K) and one fit per
-(shape, variant).   Usage: probe_pgemm_k.py OUT.jsonl [variant,variant,...]   (default pps)"""
+(shape, variant).   Usage: probe_pgemm_k.py OUT.jsonl [variant,variant,...]   (default ppp)"""
 import json
 import os
 import sys
@@ -30,7 +30,7 @@ def fit(rows):
 
 if __name__ == "__main__":
     out = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pgemm_k.jsonl"
-    variants = sys.argv[2].split(",") if len(sys.argv) > 2 else ["pps"]
+    variants = sys.argv[2].split(",") if len(sys.argv) > 2 else ["ppp"]
     fh = open(out, "a")
 
     def emit(r):

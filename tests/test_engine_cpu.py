@@ -1,4 +1,5 @@
 """CPU path of the decoder/encoder (reference ops): engine plumbing, chunked prefill, stops."""
+import pytest
 import torch
 
 from copilot_for_consensus_amd.models.decoder import DecoderModel, DecoderWeights, get_config
@@ -287,6 +288,20 @@ def test_longest_first_slots_return_caller_order(monkeypatch):
     assert eng.lpt
     got = eng.generate(prompts, 5, ignore_eos=True)
     assert got.tokens == ref.tokens and got.prompt_lens == ref.prompt_lens == [len(p) for p in prompts]
+
+
+@pytest.mark.parametrize("var", ["CFC_PGEMM_VARIANT", "CFC_PGEMM_VARIANT_SWIGLU"])
+@pytest.mark.parametrize("name", ["ring4", "ring5"])
+def test_retired_prefill_gemm_variant_fails_at_model_construction(monkeypatch, var, name):
+    """A prefill GEMM variant that no longer exists is an error when the model is built, not a
+    silent run of another kernel; the three that exist still construct."""
+    cfg = get_config("tiny")
+    monkeypatch.setenv(var, name)
+    with pytest.raises(ValueError, match=var):
+        DecoderModel(DecoderWeights.random(cfg, "cpu", seed=0))
+    for live in ("stage2", "pp", "ppp"):
+        monkeypatch.setenv(var, live)
+        DecoderModel(DecoderWeights.random(cfg, "cpu", seed=0))
 
 
 def test_prefill_tile_order_groups_sequences_by_l2_budget_heaviest_first_inside():
