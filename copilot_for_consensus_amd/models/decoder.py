@@ -485,6 +485,20 @@ class DecoderModel:
         # B <= 4 decode on the ggml-quantized weights (GGUF checkpoints; csrc/kernels/quant.hip)
         self.decode_qgemv = (weights.qlayers is not None and os.environ.get("CFC_DECODE_QGEMV", "1") != "0"
                              and weights.tp_size == 1 and weights.gate_up_interleaved and not self.fp8)
+        # B > GEMV_MAX_M decode on the same quantized copies (csrc/kernels/qdgemm.hip).  On by
+        # default up to K.QDGEMM_DEFAULT_MAX_M rows -- the largest batch bucket at which one layer's
+        # projections measured faster than on the bf16 decode GEMM (ROOFLINE.md); CFC_DECODE_QGEMM=1
+        # takes every batch the kernel supports (B <= 128), an integer n > 1 up to n rows, 0 keeps
+        # these batches on the bf16 copies.  Like the B <= 4 paths it replaces the dgemm / splitk
+        # decode modes, never an explicitly requested "lib"
+        qg = os.environ.get("CFC_DECODE_QGEMM", "")
+        if qg and not qg.isdigit():
+            raise ValueError(f"CFC_DECODE_QGEMM={qg!r}: expected 0, 1 or a row count")
+        self.qgemm_max_m = (K.QDGEMM_DEFAULT_MAX_M if qg == "" else K.QDGEMM_MAX_M if qg == "1"
+                            else min(int(qg), K.QDGEMM_MAX_M))
+        self.decode_qgemm = (weights.qlayers is not None and qg != "0"
+                             and weights.tp_size == 1 and weights.gate_up_interleaved and not self.fp8
+                             and mode in ("splitk", "dgemm"))
         # packed weights (CFC_DECODE_PACKED: auto / 1 = pack, 0 = never): one fragment-packed copy read by
         # the decode GEMM and the prefill GEMM.  The row-major copies are dropped (CFC_WEIGHTS_PACKED_ONLY:
         # auto = when the decode and prefill both run on the packed copy, 1 = always, 0 = keep both)
@@ -754,6 +768,94 @@ class DecoderModel:
                 out.append(K.rmsnorm(x, w.final_norm, eps, residual=res))
         return out
 
+    def decode_path(self, B: int, on_gpu: bool = True) -> str:
+        """What forward_decode runs a B-row step on (no side effects; forward_decode dispatches on
+        it): "qgemv" / "qgemm" -- the ggml-quantized copies on the quantized GEMV (B <= 4) / the
+        quantized decode GEMM (B <= self.qgemm_max_m); "gemv" -- the bf16 weight-streaming
+        GEMV; "dgemm" -- the hand-written bf16 decode GEMM; "splitk" -- library GEMMs with the
+        split-K residual + RMSNorm reduce; "lib" -- plain library GEMMs (CPU, fp8, TP without dgemm)."""
+        small = B <= K.GEMV_MAX_M
+        if on_gpu and self.decode_qgemm and K.GEMV_MAX_M < B <= self.qgemm_max_m:
+            return "qgemm"
+        if (self.fused_decode and on_gpu and (B <= DGEMM_MAX_ROWS or self.w.packed_only)
+                and not (small and (self.decode_gemv or self.decode_qgemv))):
+            return "dgemm"
+        if self.decode_gemm in ("splitk", "dgemm") and on_gpu and self.w.tp_size == 1:
+            if small and self.decode_qgemv:
+                return "qgemv"
+            if small and self.decode_gemv:
+                return "gemv"
+            return "splitk"
+        return "lib"
+
+    def _forward_decode_qgemm(self, x, positions, slots, ctx_lens, block_tables, kv, attn_workspace, part_blocks):
+        """4 < B <= qgemm_max_m decode straight from the GGUF blocks on the quantized decode GEMM
+        (qdgemm.hip: 3.6x / 2.4x fewer weight bytes than the bf16 copy at Q4_K / Q6_K).  Structure and rounding
+        points of _forward_decode_fused: qkv slabs (q, k, v fill one buffer with a shared split:
+        their ggml types may differ) -> RoPE / KV write / attention -> o slabs -> residual + RMSNorm
+        reduce -> gate and up slabs, interleaved 8 by 8 -> SwiGLU reduce -> down slabs -> residual +
+        RMSNorm reduce.  A projection without a quantized copy, or one the kernel does not take, runs
+        on the bf16 copy of that layer (decode GEMM, or the library when that is the decode mode)."""
+        cfg, w = self.cfg, self.w
+        B, eps, dev = x.shape[0], cfg.rms_eps, x.device
+        qs, ks = w.heads * cfg.head_dim, w.kv_heads * cfg.head_dim
+        residual = x.clone()
+        h = K.rmsnorm(x, w.layers[0]["attn_norm"], eps)
+        s_o = K.lib_split_for(qs, cfg.hidden)
+        s_d = K.lib_split_for(w.ffn, cfg.hidden)
+
+        def ok(*qws):
+            return all(q is not None and K.qdgemm_ok(B, q) for q in qws)
+
+        def slabs(split, n):
+            return K._workspace(dev, split * B * n)[:split * B * n].view(split, B, n)
+
+        for i in range(cfg.layers):
+            lw, ql = w.layers[i], w.qlayers[i]
+            pw = w.packed[i] if w.packed is not None else lw
+            if ok(ql["q"], ql["k"], ql["v"]) and qs % 4 == 0 and ks % 4 == 0:
+                bn, split = K.qdgemm_config(B, qs, cfg.hidden, ql["q"].qtype)     # q's launch: the widest
+                split = self.qkv_split or split
+                qkv = slabs(split, qs + 2 * ks)
+                K.qdgemm(h, ql["q"], "part", out=qkv, col0=0, bn=bn)
+                K.qdgemm(h, ql["k"], "part", out=qkv, col0=qs, bn=bn)
+                K.qdgemm(h, ql["v"], "part", out=qkv, col0=qs + ks, bn=bn)
+            elif self.fused_decode:
+                wq = pw["qkv"]
+                qbn, qsplit = K.dgemm_config(B, wq.shape[0], h.shape[1], bn=getattr(wq, "bn", None))
+                qsplit = self.qkv_split or qsplit
+                qkv = K.dgemm(h, wq, "part", qsplit, bn=qbn) if qsplit > 1 else K.dgemm_linear(h, wq)
+            else:
+                qkv = F.linear(h, lw["qkv"])
+            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
+                                        part_blocks)
+            a2 = attn.view(B, -1)
+            if ok(ql["o"]):
+                h = K.splitk_residual_rmsnorm(K.qdgemm(a2, ql["o"], "part"), residual, lw["mlp_norm"], eps)
+            elif self.fused_decode:
+                h = K.dgemm_residual_rmsnorm(a2, pw["o"], residual, lw["mlp_norm"], eps)
+            else:
+                h = K.lib_splitk_linear_residual_rmsnorm(a2, lw["o"], s_o, residual, lw["mlp_norm"], eps)
+            g, u = ql["gate"], ql["up"]
+            if ok(g, u) and g.N == u.N and g.N % 8 == 0:
+                bn, split = K.qdgemm_config(B, g.N, cfg.hidden, g.qtype)      # per launch: gate, then up
+                gu = slabs(split, 2 * g.N)
+                K.qdgemm(h, g, "part", out=gu, interleave="gate", bn=bn)
+                K.qdgemm(h, u, "part", out=gu, interleave="up", bn=bn)
+                a = K.splitk_reduce(gu, swiglu=True)
+            elif self.fused_decode:
+                a = K.dgemm_swiglu(h, pw["gate_up"])
+            else:
+                a = K.silu_mul(F.linear(h, lw["gate_up"]), interleaved=w.gate_up_interleaved)
+            nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
+            if ok(ql["down"]):
+                h = K.splitk_residual_rmsnorm(K.qdgemm(a, ql["down"], "part"), residual, nxt, eps)
+            elif self.fused_decode:
+                h = K.dgemm_residual_rmsnorm(a, pw["down"], residual, nxt, eps)
+            else:
+                h = K.lib_splitk_linear_residual_rmsnorm(a, lw["down"], s_d, residual, nxt, eps)
+        return h
+
     def forward_decode(self, ids, positions, slots, ctx_lens, block_tables, kv, attn_workspace=None,
                        part_blocks=16, shared_blocks=None) -> torch.Tensor:
         """One token per sequence. Returns final-normed hidden [B, H].  ``shared_blocks`` (device int32
@@ -763,11 +865,14 @@ class DecoderModel:
         cfg, w = self.cfg, self.w
         x = K.embedding(w.embed, ids)
         B = ids.shape[0]
-        if (self.fused_decode and x.is_cuda and (B <= DGEMM_MAX_ROWS or self.w.packed_only)
-                and not (B <= K.GEMV_MAX_M and (self.decode_gemv or self.decode_qgemv))):
+        path = self.decode_path(B, x.is_cuda)
+        if path == "qgemm":
+            return self._forward_decode_qgemm(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
+                                              part_blocks)
+        if path == "dgemm":
             return self._forward_decode_fused(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
                                               part_blocks)
-        if self.decode_gemm in ("splitk", "dgemm") and x.is_cuda and self.w.tp_size == 1:
+        if path != "lib":     # "qgemv" / "gemv" / "splitk": _forward_decode_splitk picks by the same rule
             return self._forward_decode_splitk(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
                                                part_blocks)
         residual = None
@@ -1042,6 +1147,11 @@ class DecoderModel:
                 and hidden.shape[0] <= K.GEMV_MAX_M and hidden.is_contiguous() and self.w.q_lm_head.N % 4 == 0
                 and K.qgemv_fits(hidden.shape[0], hidden.shape[1])):
             local = K.qgemv(hidden, self.w.q_lm_head)
+        elif (self.decode_qgemm and self.w.q_lm_head is not None and hidden.is_cuda and hidden.is_contiguous()
+                and K.GEMV_MAX_M < hidden.shape[0] <= self.qgemm_max_m
+                and K.qdgemm_ok(hidden.shape[0], self.w.q_lm_head)
+                and self.w.q_lm_head.K == hidden.shape[1] and self.w.q_lm_head.N % 4 == 0):
+            local = K.qdgemm(hidden, self.w.q_lm_head, "bf16")   # the vocab stream from its quantized copy
         elif (self.decode_gemv and hidden.is_cuda and hidden.shape[0] <= K.GEMV_MAX_M
                 and hidden.is_contiguous() and head.shape[0] % 2 == 0 and head.shape[1] % 8 == 0):
             # (the GEMV takes row pairs and 16-byte K slices: odd vocabularies, e.g. 32001-token

@@ -13,6 +13,7 @@ faiss_store.py:214).
 from __future__ import annotations
 
 import dataclasses
+import functools
 import math
 import os
 
@@ -1056,6 +1057,136 @@ def qgemv(x: torch.Tensor, qw: QWeight, epi: str = "bf16", qw2: QWeight | None =
     check(kernels().cfc_qgemv(x.data_ptr(), M, qw.N, Kd, qw.qtype, qw.buf.data_ptr(),
                               qw2.buf.data_ptr() if qw2 is not None else None, o[1], o[2], o[3],
                               mode, yf, yb, int(ldo), _stream(x)), "cfc_qgemv")
+    return out
+
+
+# ------------------------------------------------ batched decode GEMM over quantized blocks (qdgemm.hip)
+
+QDGEMM_MAX_M = 128                 # rows of X the quantized decode GEMM takes (8 MFMA row tiles)
+# largest batch the decoder sends there by default -- the measured gate (ROOFLINE.md, "Quantized decode
+# GEMM"): the summed projections of one Mistral-7B Q4_K_M layer against the bf16 decode GEMM are
+# 1.04x / 1.01x faster at M = 8 / 16 and 0.83x / 0.70x / 0.60x at 32 / 64 / 128 (the kernel is bound by its
+# dequantization instructions, not by HBM).  Correctness support stays at QDGEMM_MAX_M
+# (CFC_DECODE_QGEMM=1 dispatches every supported batch).
+QDGEMM_DEFAULT_MAX_M = 16
+QDGEMM_BNS = (128, 64, 32, 16)     # W rows per workgroup the kernel is built for (one wave per 16)
+# fitted to scripts/probes/qdgemm_probe.py --sweep on one MI355X (profiles/qdgemm_sweep.jsonl): the
+# kernel is bound by its own instruction stream, not by HBM -- a wave spends ~1.0 us per 16 x 256
+# weight block it dequantizes (gate at M = 8: 28 blocks per SIMD in 30 us) plus ~0.34 us per 16 rows
+# of X (its 8 MFMAs and their 8 LDS fragment reads; q at M = 128: 4 blocks per SIMD in 15 us)
+QDGEMM_DEQ_S = 1.0e-6
+QDGEMM_MFMA_S = 0.34e-6
+QDGEMM_LONE_S = 1.7e-6             # per block when a SIMD holds one wave (gate, 112 x 8 waves, M = 8: 27 us)
+QDGEMM_CU_RATE = 25e9              # quantized W bytes/s one CU streams (the floor under the above)
+QDGEMM_X_RATE = 90e9               # per-CU L2 -> LDS rate of the X re-reads (as DGEMM_X_RATE)
+QDGEMM_PART_RATE = 12e12           # fp32 slab traffic, bytes/s: the writes mostly stay in L2 / MALL
+QDGEMM_LAUNCH_S = 1.0e-6           # what going from one K part to several must win back
+
+
+def qdgemm_ok(M: int, qw) -> bool:
+    """Shapes and types the quantized decode GEMM takes: 1 <= M <= 128, Q8_0 / Q4_K / Q6_K,
+    N % 16 == 0, K % 256 == 0."""
+    return (isinstance(qw, QWeight) and 1 <= M <= QDGEMM_MAX_M and qw.qtype in QGEMV_TYPES
+            and qw.N > 0 and qw.N % 16 == 0 and qw.K > 0 and qw.K % 256 == 0)
+
+
+@functools.lru_cache(maxsize=None)
+def qdgemm_config(M: int, N: int, K: int, qtype: int) -> tuple[int, int]:
+    """(W rows per workgroup, split-K) of one quantized decode projection launch, by dgemm_config's
+    reasoning with the terms this kernel measures: ceil(workgroups / CUs) workgroups per CU put
+    their waves on its SIMDs, each wave walking the 256-weight blocks of its K part at a fitted
+    time per block (dequantization, constant in M, plus the MFMAs and X fragment reads per 16 rows
+    of X; a lone wave per SIMD cannot hide its load latency) -- or, if longer, the time a CU needs
+    to stream its share of the quantized bytes -- plus the fp32 slabs written and read back once
+    and one more grid ramp when split > 1.  Every workgroup stages all rows of X of its K part
+    from L2, so wider workgroups re-read X less often.  A workgroup stages X through registers, at most 16
+    16-byte pieces per thread, so bn >= 8 * row tiles (qdgemm.hip).  The K parts are whole
+    256-weight blocks and need not be equal."""
+    from ..runtime import gguf as G
+    per, size = G.BLOCK[qtype]
+    nb = K // 256
+    mt = 1 if M <= 16 else 2 if M <= 32 else 4 if M <= 64 else 8
+    best = None
+    for bn in QDGEMM_BNS:
+        # measured: 128-row workgroups win from 64 rows of X up (half the X re-reads), 64-row ones
+        # are as fast or faster below (q, o, down, lm_head at M = 8 and 32)
+        if bn < 8 * mt or (bn == 128 and mt <= 2):
+            continue
+        tiles = -(-N // bn)
+        for split in range(1, nb + 1):
+            if split > 1 and tiles * split > 4 * DGEMM_CUS:     # past 4 workgroups per CU more parts only add slabs
+                break
+            blk = -(-nb // split)                  # blocks of the longest part
+            # waves a SIMD runs one after the other (workgroups are indivisible: ceil per CU); a
+            # wave alone on its SIMD waits out its loads instead (QDGEMM_LONE_S per block)
+            per_cu = -(-tiles * split // DGEMM_CUS)
+            waves = -(-per_cu * bn // 64)
+            math = blk * (max(waves * (QDGEMM_DEQ_S + mt * QDGEMM_MFMA_S), QDGEMM_LONE_S)
+                          + per_cu * mt * 16 * 512 / QDGEMM_X_RATE)     # + each workgroup's X tile from L2
+            stream = -(-tiles * split // DGEMM_CUS) * blk * bn * 256 * size / per / QDGEMM_CU_RATE
+            t = max(math, stream) + QDGEMM_LAUNCH_S * (split > 1)
+            if split > 1:
+                t += 2 * split * M * N * 4 / QDGEMM_PART_RATE
+            if best is None or t < best[0] - 1e-12:
+                best = (t, bn, split)
+    return best[1], best[2]
+
+
+def qdgemm(x: torch.Tensor, qw: "QWeight", epi: str = "part", split: int | None = None,
+           out: torch.Tensor | None = None, col0: int = 0, interleave: str | None = None,
+           bn: int | None = None) -> torch.Tensor:
+    """x [M <= 128, K] bf16 @ dequant(qw)^T on the quantized decode GEMM (qdgemm.hip), one launch.
+    ``epi`` "part": fp32 split-K slabs into columns [col0, col0 + N) of ``out`` [split, M, W] (a
+    strided view is fine; default: [split, M, N] of the split-K workspace); "bf16" (split 1): bf16
+    rows into ``out`` [M, W].  ``interleave`` "gate" / "up": the weight is one half of an 8-row
+    interleaved gate/up pair -- its row j goes to column col0 + 16 (j // 8) + j % 8 (+ 8 for up)
+    of a 2 N wide range, the layout splitk_reduce(swiglu=True) reads.  Returns ``out``."""
+    if x.dim() != 2 or not isinstance(qw, QWeight):
+        raise ValueError("qdgemm: x must be [M, K] and qw a QWeight")
+    M, Kd = x.shape
+    if Kd != qw.K or not qdgemm_ok(M, qw):
+        raise ValueError(f"qdgemm: x {tuple(x.shape)} vs weight [{qw.N}, {qw.K}] type {qw.qtype} "
+                         f"(M <= {QDGEMM_MAX_M}, N % 16 == 0, K % 256 == 0)")
+    if epi not in ("part", "bf16"):
+        raise ValueError(f"qdgemm: epi {epi!r}: expected part or bf16")
+    if interleave not in (None, "gate", "up"):
+        raise ValueError(f"qdgemm: interleave {interleave!r}: expected None, gate or up")
+    _req(x, torch.bfloat16, "x")
+    if epi == "bf16":
+        if split not in (None, 1):
+            raise ValueError("qdgemm: the bf16 epilogue needs split 1")
+        split = 1
+    elif split is None and out is not None:
+        split = out.shape[0]
+    if bn is None or split is None:
+        cbn, csplit = qdgemm_config(M, qw.N, Kd, qw.qtype)
+        bn, split = bn or cbn, split or csplit
+    if not 1 <= split <= Kd // 256:
+        raise ValueError(f"qdgemm: split {split} outside 1 .. K / 256 = {Kd // 256}")
+    width = 2 * qw.N if interleave else qw.N
+    if col0 < 0 or col0 % 4:
+        raise ValueError(f"qdgemm: col0 {col0} must be a non-negative multiple of 4")
+    dtype = torch.float32 if epi == "part" else torch.bfloat16
+    lead = (split, M) if epi == "part" else (M,)
+    if out is None:
+        if epi == "part":
+            n = split * M * (col0 + width)
+            out = _workspace(x.device, n)[:n].view(split, M, col0 + width)
+        else:
+            out = torch.empty(M, col0 + width, dtype=dtype, device=x.device)
+    if (out.dtype != dtype or out.device != x.device or tuple(out.shape[:-1]) != lead or out.stride(-1) != 1
+            or col0 + width > out.shape[-1]):
+        raise ValueError(f"qdgemm: out {tuple(out.shape)} {out.dtype} does not hold {lead} x columns "
+                         f"[{col0}, {col0 + width})")
+    ptr = out.data_ptr() + col0 * out.element_size()
+    slab = out.stride(0) if epi == "part" else 0
+    if out.stride(-2) % 4 or slab % 4 or ptr % (16 if epi == "part" else 8):
+        raise ValueError(f"qdgemm: out strides {tuple(out.stride())} / column {col0} break the 16-byte stores")
+    o = tuple(qw.offs) + (0,) * (4 - len(qw.offs))
+    check(kernels().cfc_qdgemm(x.data_ptr(), M, qw.N, Kd, qw.qtype, qw.buf.data_ptr(), o[1], o[2], o[3],
+                               0 if epi == "part" else 1, split, bn, {None: 0, "gate": 1, "up": 2}[interleave],
+                               ptr if epi == "part" else None, None if epi == "part" else ptr,
+                               int(slab), int(out.stride(-2)), _stream(x)), "cfc_qdgemm")
     return out
 
 

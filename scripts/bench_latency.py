@@ -9,6 +9,12 @@ the prompt + first token) and decode tokens/s (tokens after the first / decode w
 over ``--reps`` runs.  The prefix cache is off so every run prefills the whole prompt.
 
     python scripts/bench_latency.py --models mistral-7b llama-2-7b llama-2-13b --prompt 512 2500
+
+``--batch B`` decodes B such requests together (one engine call; decode tokens/s is then the sum
+over the batch); with quantized weights ``--ab-qgemm`` runs every point twice in the same process,
+on the quantized decode GEMM and with ``CFC_DECODE_QGEMM=0`` (the bf16 copies above B = 4).
+
+    python scripts/bench_latency.py --models mistral-7b --weights q4_k_m --batch 8 --ab-qgemm
 """
 import argparse
 import json
@@ -33,7 +39,7 @@ PUBLISHED = {
 }
 
 
-def run_model(name, prompt_lens, new, reps, seed, weights="bf16"):
+def run_model(name, prompt_lens, new, reps, seed, weights="bf16", batch=1, ab_qgemm=False):
     cfg = get_config(name)
     dev = torch.device("cuda")
     w = DecoderWeights.random(cfg, dev, seed=seed)
@@ -44,40 +50,61 @@ def run_model(name, prompt_lens, new, reps, seed, weights="bf16"):
         from copilot_for_consensus_amd.ops.kernels import attach_random_quant
         attach_random_quant(w, weights, seed)
         wbytes = sum(q.nbytes for layer in w.qlayers for q in layer.values()) + w.q_lm_head.nbytes
-    model = DecoderModel(w)
-    if weights != "bf16":
-        assert model.decode_qgemv
-    kv = PagedKVCache(cfg.layers, blocks_needed(max(prompt_lens) + new) + 8, cfg.kv_heads, cfg.head_dim, dev)
-    eng = LLMEngine(model, kv, max_prefill_tokens=16384, prefix_cache=False)
+    engines = []
+    for flag in (("1", "0") if ab_qgemm and weights != "bf16" else (None,)):
+        saved = os.environ.get("CFC_DECODE_QGEMM")
+        if flag is not None:
+            os.environ["CFC_DECODE_QGEMM"] = flag
+        try:
+            model = DecoderModel(w)
+        finally:
+            if flag is not None:
+                os.environ.pop("CFC_DECODE_QGEMM")
+                if saved is not None:
+                    os.environ["CFC_DECODE_QGEMM"] = saved
+        if weights != "bf16":
+            assert model.decode_qgemv
+        kv = PagedKVCache(cfg.layers, batch * blocks_needed(max(prompt_lens) + new) + 8, cfg.kv_heads, cfg.head_dim,
+                          dev)
+        engines.append(LLMEngine(model, kv, max_prefill_tokens=16384, prefix_cache=False))
     g = torch.Generator().manual_seed(seed)
     rows = []
     for plen in prompt_lens:
-        prompt = [cfg.bos_id] + torch.randint(3, cfg.vocab_size, (plen - 1,), generator=g).tolist()
-        eng.generate([prompt], max_new_tokens=new, ignore_eos=True)      # capture the graph, warm GEMMs
-        ttft, tps = [], []
+        prompts = [[cfg.bos_id] + torch.randint(3, cfg.vocab_size, (plen - 1,), generator=g).tolist()
+                   for _ in range(batch)]
+        for eng in engines:
+            eng.generate(prompts, max_new_tokens=new, ignore_eos=True)      # capture the graph, warm GEMMs
+        stats = [([], []) for _ in engines]
         for _ in range(reps):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = eng.generate([prompt], max_new_tokens=new, ignore_eos=True)
-            torch.cuda.synchronize()
-            wall = time.perf_counter() - t0
-            ttft.append(res.ttft_s)
-            tps.append((len(res.tokens[0]) - 1) / max(wall - res.ttft_s, 1e-9))
-        row = {"model": name, "prompt_tokens": plen, "new_tokens": new, "ttft_s": round(statistics.median(ttft), 4),
-               "decode_tok_s": round(statistics.median(tps), 1),
-               "ms_per_token": round(1000.0 / statistics.median(tps), 3),
-               "weights": weights, "weight_gb": round(wbytes / 1e9, 2)}
-        # HBM bytes one decode step must read: all weights + the KV of the context so far
-        kv_bytes = 2 * cfg.layers * cfg.kv_heads * cfg.head_dim * 2 * (plen + new / 2)
-        row["achieved_TB_s"] = round((wbytes + kv_bytes) * statistics.median(tps) / 1e12, 2)
-        pub = PUBLISHED.get(name)
-        if pub:
-            row["published_tok_s"] = pub["tok_s"]
-            row["published_hw"] = pub["hw"]
-            row["vs_published"] = round(row["decode_tok_s"] / pub["tok_s"], 2)
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    del eng, kv, model
+            for eng, (ttft, tps) in zip(engines, stats):      # the engines alternate rep by rep
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = eng.generate(prompts, max_new_tokens=new, ignore_eos=True)
+                torch.cuda.synchronize()
+                wall = time.perf_counter() - t0
+                ttft.append(res.ttft_s)
+                tps.append(sum(len(t) - 1 for t in res.tokens) / max(wall - res.ttft_s, 1e-9))
+        for eng, (ttft, tps) in zip(engines, stats):
+            row = {"model": name, "prompt_tokens": plen, "new_tokens": new, "ttft_s": round(statistics.median(ttft), 4),
+                   "decode_tok_s": round(statistics.median(tps), 1),
+                   "ms_per_token": round(1000.0 / statistics.median(tps), 3),
+                   "weights": weights, "weight_gb": round(wbytes / 1e9, 2)}
+            if batch > 1:
+                row["batch"] = batch
+                row["decode_path"] = eng.model.decode_path(batch)
+            row["decode_qgemm"] = bool(eng.model.decode_qgemm)
+            # HBM bytes one decode step must read: all weights + the KV of the context so far
+            kv_bytes = 2 * cfg.layers * cfg.kv_heads * cfg.head_dim * 2 * (plen + new / 2)
+            # (a batch shares the weight read: steps/s = tok/s / batch, every request's KV is read each step)
+            row["achieved_TB_s"] = round((wbytes + batch * kv_bytes) * statistics.median(tps) / batch / 1e12, 2)
+            pub = PUBLISHED.get(name)
+            if pub:
+                row["published_tok_s"] = pub["tok_s"]
+                row["published_hw"] = pub["hw"]
+                row["vs_published"] = round(row["decode_tok_s"] / pub["tok_s"], 2)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    del engines, eng, kv, model
     torch.cuda.empty_cache()
     return rows
 
@@ -91,9 +118,12 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weights", choices=["bf16", "q4_k_m", "q8_0"], default="bf16",
                     help="decode weight format (q4_k_m / q8_0: ggml blocks streamed by the quantized GEMV)")
+    ap.add_argument("--batch", type=int, default=1, help="requests decoded together (decode tok/s: their sum)")
+    ap.add_argument("--ab-qgemm", action="store_true",
+                    help="quantized weights: every point also with CFC_DECODE_QGEMM=0, the two alternating")
     a = ap.parse_args()
     for name in a.models:
-        run_model(name, a.prompt, a.new, a.reps, a.seed, a.weights)
+        run_model(name, a.prompt, a.new, a.reps, a.seed, a.weights, a.batch, a.ab_qgemm)
 
 
 if __name__ == "__main__":
