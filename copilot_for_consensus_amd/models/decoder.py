@@ -143,6 +143,10 @@ class DecoderWeights:
         self.packed: list[dict] | None = None
         self.packed_lm_head = None
         self.packed_only = False      # row-major projections dropped after packing
+        # the projections exist as ggml-quantized blocks only (from_gguf(resident="quant") /
+        # to_quant_only()): layers[i][projection] and packed are None, the bf16 consumers read a
+        # scratch of scratch_numel() values that DecoderModel re-fills from the blocks
+        self.quant_only = False
         self.cos_sin = rope_cos_sin(cfg.max_positions, cfg.head_dim, cfg.rope_theta, device=self.device,
                                     llama3_scaling=cfg.rope_llama3)
 
@@ -226,19 +230,28 @@ class DecoderWeights:
         return w.finalize()
 
     @classmethod
-    def from_gguf(cls, path, device, cfg=None, quantized_decode: bool = True):
+    def from_gguf(cls, path, device, cfg=None, quantized_decode: bool = True, resident: str = "bf16"):
         """Load a llama-architecture GGUF (llama.cpp / Ollama files: Mistral, Llama).  Every tensor
         is dequantized to bf16 (GPU kernel on CUDA devices) for the batched paths; with
         ``quantized_decode`` the Q4_K / Q6_K / Q8_0 projection weights are ALSO kept in their
         block format for the B <= 4 decode GEMV (``qlayers`` / ``q_lm_head``).  q/k rows are
         un-permuted from llama.cpp's interleaved-RoPE order to this framework's rotate-half order.
-        TP is not supported for GGUF checkpoints (one GPU holds any GGUF model)."""
+        TP is not supported for GGUF checkpoints (one GPU holds any GGUF model).
+
+        ``resident="quant"``: the projections are loaded as quantized blocks ONLY (no bf16 copy is
+        ever made; ``quant_only``), which needs every projection 2-D, Q4_K / Q6_K / Q8_0 with
+        K % 256 == 0 and a GPU; norms and the embedding stay bf16, the lm_head stays quantized when
+        ``output.weight`` has a supported type and bf16 otherwise (tied to the embedding included)."""
         from ..ops.kernels import QGEMV_TYPES, QWeight, dequant_bf16
         from ..runtime import gguf as G
 
+        if resident not in ("bf16", "quant"):
+            raise ValueError(f"resident={resident!r}: expected bf16 or quant")
         r = G.GGUFReader(path)
         cfg = cfg or G.config_from_gguf(r.metadata, tensor_names=r.tensors.keys(), name=Path(path).stem)
         w = cls(cfg, device)
+        if resident == "quant":
+            return w._load_gguf_quant_only(r, path)
         D = cfg.head_dim
         qrows = G.unpermute_qk_rows(cfg.heads * D, cfg.heads)
         krows = G.unpermute_qk_rows(cfg.kv_heads * D, cfg.kv_heads)
@@ -287,6 +300,109 @@ class DecoderWeights:
             w.q_lm_head = quant(head)
         w.gguf_types = sorted({t.type_name for t in r.tensors.values()})
         return w.finalize()
+
+    GGUF_PROJECTIONS = {"q": "attn_q", "k": "attn_k", "v": "attn_v", "o": "attn_output", "gate": "ffn_gate",
+                        "up": "ffn_up", "down": "ffn_down"}
+
+    def _load_gguf_quant_only(self, r, path) -> "DecoderWeights":
+        """from_gguf(resident="quant"): QWeights for the projections, bf16 for the rest."""
+        from ..ops.kernels import QGEMV_TYPES, QWeight, dequant_bf16
+        from ..runtime import gguf as G
+
+        cfg, D = self.cfg, self.cfg.head_dim
+        names = [f"blk.{i}.{t}.weight" for i in range(cfg.layers) for t in self.GGUF_PROJECTIONS.values()]
+        missing = [n for n in names if n not in r.tensors]
+        if missing:
+            raise KeyError(f"{path}: tensor {missing[0]} missing")
+        bad = [f"{n} ({r.tensors[n].type_name} {tuple(r.tensors[n].shape)})" for n in names
+               if len(r.tensors[n].shape) != 2 or r.tensors[n].ggml_type not in QGEMV_TYPES
+               or r.tensors[n].shape[1] % 256 or r.tensors[n].shape[0] % 16]
+        if bad:
+            raise ValueError(f"{path}: resident='quant' needs every projection 2-D Q4_K / Q6_K / Q8_0 with "
+                             f"N % 16 == 0 and K % 256 == 0; not so: {', '.join(bad)}")
+        if self.device.type != "cuda":
+            raise ValueError("resident='quant' needs a GPU: the quantized kernels have no CPU path")
+        rows = {"q": G.unpermute_qk_rows(cfg.heads * D, cfg.heads), "k": G.unpermute_qk_rows(cfg.kv_heads * D, cfg.kv_heads)}
+
+        def bf16(name):
+            ti = r.tensors[name]
+            return dequant_bf16(ti.data, ti.ggml_type, ti.shape, self.device).contiguous()
+
+        def quant(name, perm=None):
+            ti = r.tensors[name]
+            return QWeight.from_raw(ti.data, ti.ggml_type, ti.shape[0], ti.shape[1], self.device, rows=perm)
+
+        self.qlayers = []
+        for i in range(cfg.layers):
+            p = f"blk.{i}."
+            self.layers.append({"attn_norm": bf16(p + "attn_norm.weight"), "qkv": None, "o": None,
+                                "mlp_norm": bf16(p + "ffn_norm.weight"), "gate_up": None, "down": None})
+            self.qlayers.append({k: quant(p + t + ".weight", rows.get(k)) for k, t in self.GGUF_PROJECTIONS.items()})
+        self.embed = bf16("token_embd.weight")
+        self.final_norm = bf16("output_norm.weight")
+        head = r.tensors.get("output.weight")
+        hname = "output.weight" if head is not None else "token_embd.weight"
+        if len(r.tensors[hname].shape) == 2 and r.tensors[hname].ggml_type in QGEMV_TYPES:
+            self.q_lm_head = quant(hname)
+        # the quantized head alone serves every batch only when the quantized decode GEMM takes it;
+        # an odd vocabulary keeps the bf16 head as well (as a tied or otherwise-typed head does)
+        if self.q_lm_head is None or head is None or head.shape[0] % 16 or head.shape[1] % 256:
+            self.lm_head = self.embed if head is None else bf16("output.weight")
+        self.gguf_types = sorted({t.type_name for t in r.tensors.values()})
+        self.gate_up_interleaved = True     # the scratch is filled 8-row interleaved (K.qunpack)
+        self.quant_only = True
+        return self
+
+    def to_quant_only(self) -> "DecoderWeights":
+        """Drop the bf16 and packed projections of a model whose ``qlayers`` are complete (every
+        projection a QWeight the unpack kernel takes), e.g. after K.attach_random_quant, so that
+        the quantized-blocks-only residency can be benchmarked without a file.  The bf16 lm_head
+        goes too when ``q_lm_head`` exists."""
+        if self.quant_only:
+            return self
+        if self.device.type != "cuda" or self.tp_size != 1 or self.fp8_layers is not None:
+            raise ValueError("to_quant_only needs one GPU and bf16 (not fp8) weights")
+        if self.qlayers is None or len(self.qlayers) != len(self.layers) or not all(
+                isinstance(ql.get(k), K.QWeight) and K.qunpack_ok(ql[k], K.DGEMM_BNS[0])
+                for ql in self.qlayers for k in self.GGUF_PROJECTIONS):
+            raise ValueError("to_quant_only needs a Q4_K / Q6_K / Q8_0 copy of every projection (qlayers)")
+        for layer in self.layers:
+            for k in self.DECODE_PACKED:
+                layer[k] = None
+        self.packed, self.packed_only, self.packed_lm_head = None, False, None
+        if self.q_lm_head is not None and K.qunpack_ok(self.q_lm_head, K.DGEMM_BNS[0]):
+            self.lm_head = None
+        self.gate_up_interleaved = True
+        self.quant_only = True
+        torch.cuda.empty_cache()
+        return self
+
+    def projection_shapes(self) -> dict[str, tuple[int, int]]:
+        """(N, K) of this rank's four projections."""
+        cfg, D = self.cfg, self.cfg.head_dim
+        return {"qkv": ((self.heads + 2 * self.kv_heads) * D, cfg.hidden), "o": (cfg.hidden, self.heads * D),
+                "gate_up": (2 * self.ffn, cfg.hidden), "down": (cfg.hidden, self.ffn)}
+
+    def scratch_numel(self) -> int:
+        """bf16 values of the scratch a quant-only model unpacks one projection at a time into."""
+        return max(n * k for n, k in self.projection_shapes().values())
+
+    def resident_bytes(self) -> dict[str, int]:
+        """HBM the weights hold, by kind: ``quant`` (ggml blocks), ``bf16_projections`` (row-major
+        and packed copies of the projections), ``bf16_other`` (norms, embedding, lm_head and its
+        packed copy), ``scratch`` (the unpack scratch DecoderModel allocates for quant-only weights)."""
+        def nb(t):
+            return 0 if t is None else t.numel() * t.element_size()
+        quant = sum(q.buf.numel() for ql in self.qlayers or [] for q in ql.values() if q is not None)
+        quant += self.q_lm_head.buf.numel() if self.q_lm_head is not None else 0
+        proj = sum(nb(layer.get(k)) for layer in self.layers for k in self.DECODE_PACKED)
+        proj += sum(p.nbytes() for layer in self.packed or [] for p in layer.values())
+        other = sum(nb(t) for layer in self.layers for k, t in layer.items() if k not in self.DECODE_PACKED)
+        other += nb(self.embed) + nb(self.final_norm)
+        other += nb(self.lm_head) if self.lm_head is not self.embed else 0
+        other += self.packed_lm_head.nbytes() if self.packed_lm_head is not None else 0
+        return {"quant": quant, "bf16_projections": proj, "bf16_other": other,
+                "scratch": 2 * self.scratch_numel() if self.quant_only else 0}
 
     def finalize(self) -> "DecoderWeights":
         """Put gate/up rows in the 8-row interleaved order the fused decode SwiGLU GEMM reads (the
@@ -356,6 +472,13 @@ class DecoderWeights:
         for k in self.DECODE_PACKED:
             if out.get(k) is None and self.packed is not None:
                 out[k] = K._rowmajor(self.packed[i][k])
+        if self.quant_only:
+            # dequantized from the blocks (CPU, K.QWeight.to_rowmajor_bf16): q / k / v concatenated,
+            # gate / up interleaved as finalize() does
+            ql = {k: q.to_rowmajor_bf16().to(self.device) for k, q in self.qlayers[i].items()}
+            out["qkv"] = torch.cat([ql["q"], ql["k"], ql["v"]], 0).contiguous()
+            out["gate_up"] = interleave_gate_up(torch.cat([ql["gate"], ql["up"]], 0))
+            out["o"], out["down"] = ql["o"], ql["down"]
         return out
 
     def nbytes(self) -> int:
@@ -364,7 +487,8 @@ class DecoderWeights:
         n += self.packed_lm_head.nbytes() if self.packed_lm_head is not None else 0
         for q in self.fp8_layers or []:
             n += sum(a.numel() * a.element_size() + b.numel() * b.element_size() for a, b in q.values())
-        return n + sum(t.numel() * t.element_size() for t in (self.embed, self.final_norm, self.lm_head))
+        return n + sum(t.numel() * t.element_size() for t in (self.embed, self.final_norm, self.lm_head)
+                       if t is not None)
 
 
 def load_config_json(path) -> DecoderConfig:
@@ -502,7 +626,10 @@ class DecoderModel:
         # packed weights (CFC_DECODE_PACKED: auto / 1 = pack, 0 = never): one fragment-packed copy read by
         # the decode GEMM and the prefill GEMM.  The row-major copies are dropped (CFC_WEIGHTS_PACKED_ONLY:
         # auto = when the decode and prefill both run on the packed copy, 1 = always, 0 = keep both)
-        if (self.fused_decode or self.prefill_gemm == "hip") and weights.device.type == "cuda":
+        self._scratch = None
+        if weights.quant_only:
+            self._init_quant_only(qg)
+        elif (self.fused_decode or self.prefill_gemm == "hip") and weights.device.type == "cuda":
             pk = self._packing()
             if pk is not None:
                 weights.pack_decode(drop_rowmajor=pk == "only")
@@ -548,6 +675,56 @@ class DecoderModel:
         free, total = torch.cuda.mem_get_info(self.w.device)
         return "both" if free - self.w.packed_bytes() > self.PACKED_FREE_FRACTION * total else None
 
+    def _init_quant_only(self, qg: str) -> None:
+        """Weights resident as ggml-quantized blocks only (DecoderWeights.quant_only): B <= 4 decodes
+        on the quantized GEMV, 5 <= B <= 128 on the quantized decode GEMM, and every consumer that
+        needs bf16 fragments (the prefill GEMM, B > 128, a projection the quantized kernels do not
+        take) reads ONE scratch of max(N K) bf16 that _scratch_weight re-fills from the blocks just
+        before the read.  The four views on it are packed for the tile widths pack_decode() picks,
+        so whatever reads them computes what the bf16-resident model computes.
+
+        The scratch is written and read on the caller's stream; stream order is all that keeps a
+        projection's GEMM ahead of the next projection's unpack.  Two streams must therefore never
+        run one model's projections concurrently (nothing does: the overlapped prefill is TP-only)."""
+        w = self.w
+        if not (self.prefill_gemm == "hip" and self.decode_gemm == "dgemm" and w.tp_size == 1 and not self.fp8
+                and w.gate_up_interleaved and self._dgemm_shapes() and w.device.type == "cuda"):
+            raise ValueError("quantized-blocks-only weights need CFC_DECODE_GEMM=dgemm and CFC_PREFILL_GEMM=hip on one "
+                             "GPU, no fp8, and projections the decode GEMM takes (N, K % 64)")
+        if qg == "0" or os.environ.get("CFC_DECODE_QGEMV", "1") == "0":
+            raise ValueError("quantized-blocks-only weights decode on the quantized kernels: CFC_DECODE_QGEMM=0 / "
+                             "CFC_DECODE_QGEMV=0 have no bf16 copy to fall back on")
+        self.decode_qgemv = self.decode_qgemm = True
+        self.decode_gemv = False
+        self.qgemm_max_m = K.QDGEMM_MAX_M
+        data = torch.empty(w.scratch_numel(), dtype=torch.bfloat16, device=w.device)   # never reallocated
+        self._scratch_data = data
+        self._scratch = {name: K.PackedWeight(data[:n * k], n, k, K.dgemm_config(128, n, k, swiglu=name == "gate_up")[0])
+                         for name, (n, k) in w.projection_shapes().items()}
+
+    def _scratch_weight(self, i: int, name: str) -> "K.PackedWeight":
+        """Projection ``name`` of layer ``i`` unpacked from its quantized blocks into the scratch
+        (current stream): q, k, v side by side, gate / up 8-row interleaved.  The view is valid
+        until the next call."""
+        pw, ql = self._scratch[name], self.w.qlayers[i]
+        if name == "qkv":
+            K.qunpack(ql["q"], pw)
+            K.qunpack(ql["k"], pw, row0=ql["q"].N)
+            K.qunpack(ql["v"], pw, row0=ql["q"].N + ql["k"].N)
+        elif name == "gate_up":
+            K.qunpack(ql["gate"], pw, interleave="gate")
+            K.qunpack(ql["up"], pw, interleave="up")
+        else:
+            K.qunpack(ql[name], pw)
+        return pw
+
+    def _decode_weight(self, i: int, name: str):
+        """What the bf16 decode GEMM reads for projection ``name`` of layer ``i``: the packed copy,
+        the row-major one, or (quantized-blocks-only weights) the freshly filled scratch view."""
+        if self.w.quant_only:
+            return self._scratch_weight(i, name)
+        return (self.w.packed[i] if self.w.packed is not None else self.w.layers[i])[name]
+
     def _dgemm_shapes(self) -> bool:
         """Every decode projection of this rank fits the decode GEMM (N % 64, K % 64)."""
         w, D = self.w, self.cfg.head_dim
@@ -578,8 +755,15 @@ class DecoderModel:
     def _plin(self, i: int, name: str, x: torch.Tensor, epi: str = "bf16") -> torch.Tensor:
         """Prefill projection (``epi`` "swiglu" returns silu(gate) * up of the interleaved gate/up
         weights): the hand-written pgemm on the packed weight when selected and the shape fits;
-        fewer rows than one pgemm tile on the decode GEMM (same packed weight); else the library."""
-        pw = self.w.packed[i][name] if self.w.packed is not None else None
+        fewer rows than one pgemm tile on the decode GEMM (same packed weight); else the library.
+        Quantized-blocks-only weights: the packed weight is the scratch, filled here."""
+        if self.w.quant_only:
+            if not (x.is_cuda and x.is_contiguous() and K.dgemm_ok(x, self._scratch[name])):
+                raise ValueError(f"prefill {name}: x {tuple(x.shape)} {x.dtype} does not fit the hand-written GEMMs "
+                                 "and quantized-blocks-only weights have no bf16 copy for the library")
+            pw = self._scratch_weight(i, name)
+        else:
+            pw = self.w.packed[i][name] if self.w.packed is not None else None
         wt = pw if pw is not None else self.w.layers[i][name]
         if self.prefill_gemm == "hip" and x.is_cuda and x.is_contiguous() and (
                 epi != "swiglu" or self.w.gate_up_interleaved):
@@ -773,8 +957,13 @@ class DecoderModel:
         it): "qgemv" / "qgemm" -- the ggml-quantized copies on the quantized GEMV (B <= 4) / the
         quantized decode GEMM (B <= self.qgemm_max_m); "gemv" -- the bf16 weight-streaming
         GEMV; "dgemm" -- the hand-written bf16 decode GEMM; "splitk" -- library GEMMs with the
-        split-K residual + RMSNorm reduce; "lib" -- plain library GEMMs (CPU, fp8, TP without dgemm)."""
+        split-K residual + RMSNorm reduce; "lib" -- plain library GEMMs (CPU, fp8, TP without dgemm);
+        "scratch" -- quantized-blocks-only weights at a batch the quantized kernels do not take: the
+        bf16 decode GEMM on the scratch each projection is unpacked into just before (where a model
+        with bf16 copies would return "dgemm", "gemv" or "splitk")."""
         small = B <= K.GEMV_MAX_M
+        if self.w.quant_only:
+            return "qgemv" if small else "qgemm" if B <= self.qgemm_max_m else "scratch"
         if on_gpu and self.decode_qgemm and K.GEMV_MAX_M < B <= self.qgemm_max_m:
             return "qgemm"
         if (self.fused_decode and on_gpu and (B <= DGEMM_MAX_ROWS or self.w.packed_only)
@@ -812,7 +1001,6 @@ class DecoderModel:
 
         for i in range(cfg.layers):
             lw, ql = w.layers[i], w.qlayers[i]
-            pw = w.packed[i] if w.packed is not None else lw
             if ok(ql["q"], ql["k"], ql["v"]) and qs % 4 == 0 and ks % 4 == 0:
                 bn, split = K.qdgemm_config(B, qs, cfg.hidden, ql["q"].qtype)     # q's launch: the widest
                 split = self.qkv_split or split
@@ -821,7 +1009,7 @@ class DecoderModel:
                 K.qdgemm(h, ql["k"], "part", out=qkv, col0=qs, bn=bn)
                 K.qdgemm(h, ql["v"], "part", out=qkv, col0=qs + ks, bn=bn)
             elif self.fused_decode:
-                wq = pw["qkv"]
+                wq = self._decode_weight(i, "qkv")
                 qbn, qsplit = K.dgemm_config(B, wq.shape[0], h.shape[1], bn=getattr(wq, "bn", None))
                 qsplit = self.qkv_split or qsplit
                 qkv = K.dgemm(h, wq, "part", qsplit, bn=qbn) if qsplit > 1 else K.dgemm_linear(h, wq)
@@ -833,7 +1021,7 @@ class DecoderModel:
             if ok(ql["o"]):
                 h = K.splitk_residual_rmsnorm(K.qdgemm(a2, ql["o"], "part"), residual, lw["mlp_norm"], eps)
             elif self.fused_decode:
-                h = K.dgemm_residual_rmsnorm(a2, pw["o"], residual, lw["mlp_norm"], eps)
+                h = K.dgemm_residual_rmsnorm(a2, self._decode_weight(i, "o"), residual, lw["mlp_norm"], eps)
             else:
                 h = K.lib_splitk_linear_residual_rmsnorm(a2, lw["o"], s_o, residual, lw["mlp_norm"], eps)
             g, u = ql["gate"], ql["up"]
@@ -844,14 +1032,14 @@ class DecoderModel:
                 K.qdgemm(h, u, "part", out=gu, interleave="up", bn=bn)
                 a = K.splitk_reduce(gu, swiglu=True)
             elif self.fused_decode:
-                a = K.dgemm_swiglu(h, pw["gate_up"])
+                a = K.dgemm_swiglu(h, self._decode_weight(i, "gate_up"))
             else:
                 a = K.silu_mul(F.linear(h, lw["gate_up"]), interleaved=w.gate_up_interleaved)
             nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
             if ok(ql["down"]):
                 h = K.splitk_residual_rmsnorm(K.qdgemm(a, ql["down"], "part"), residual, nxt, eps)
             elif self.fused_decode:
-                h = K.dgemm_residual_rmsnorm(a, pw["down"], residual, nxt, eps)
+                h = K.dgemm_residual_rmsnorm(a, self._decode_weight(i, "down"), residual, nxt, eps)
             else:
                 h = K.lib_splitk_linear_residual_rmsnorm(a, lw["down"], s_d, residual, nxt, eps)
         return h
@@ -869,7 +1057,7 @@ class DecoderModel:
         if path == "qgemm":
             return self._forward_decode_qgemm(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
                                               part_blocks)
-        if path == "dgemm":
+        if path in ("dgemm", "scratch"):
             return self._forward_decode_fused(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
                                               part_blocks)
         if path != "lib":     # "qgemv" / "gemv" / "splitk": _forward_decode_splitk picks by the same rule
@@ -936,24 +1124,27 @@ class DecoderModel:
         tp = w.tp_size > 1
         for i in range(cfg.layers):
             lw = w.layers[i]
-            pw = w.packed[i] if w.packed is not None else lw    # fragment-packed copies when present
-            wq = pw["qkv"]
+            # fragment-packed copies when present; quantized-blocks-only weights: the one scratch,
+            # unpacked for each projection right before its GEMM (so fetched in order of use)
+            wq = self._decode_weight(i, "qkv")
             qbn, qsplit = K.dgemm_config(B, wq.shape[0], h.shape[1], bn=getattr(wq, "bn", None))
             qsplit = self.qkv_split or qsplit
             # split-K slabs go straight into RoPE / KV write (the reduce folded in)
             qkv = K.dgemm(h, wq, "part", qsplit, bn=qbn) if qsplit > 1 else K.dgemm_linear(h, wq)
             attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
                                         part_blocks)
+            wo = self._decode_weight(i, "o")
             if tp:
-                h = self._tp_residual_rmsnorm(attn.view(B, -1), pw["o"], residual, lw["mlp_norm"], eps)
+                h = self._tp_residual_rmsnorm(attn.view(B, -1), wo, residual, lw["mlp_norm"], eps)
             else:
-                h = K.dgemm_residual_rmsnorm(attn.view(B, -1), pw["o"], residual, lw["mlp_norm"], eps)
-            a = K.dgemm_swiglu(h, pw["gate_up"])
+                h = K.dgemm_residual_rmsnorm(attn.view(B, -1), wo, residual, lw["mlp_norm"], eps)
+            a = K.dgemm_swiglu(h, self._decode_weight(i, "gate_up"))
             nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
+            wd = self._decode_weight(i, "down")
             if tp:
-                h = self._tp_residual_rmsnorm(a, pw["down"], residual, nxt, eps)
+                h = self._tp_residual_rmsnorm(a, wd, residual, nxt, eps)
             else:
-                h = K.dgemm_residual_rmsnorm(a, pw["down"], residual, nxt, eps)
+                h = K.dgemm_residual_rmsnorm(a, wd, residual, nxt, eps)
         return h
 
     def _tp_residual_rmsnorm(self, x, w, residual, norm_w, eps):
@@ -1064,8 +1255,9 @@ class DecoderModel:
     def _forward_decode_qgemv(self, h, residual, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
                               part_blocks):
         """B <= 4 decode straight from the GGUF blocks (Q4_K / Q6_K / Q8_0 weight stream, 3.6x fewer
-        bytes than bf16 at Q4_K).  Projections without a quantized copy use the bf16 GEMV.  Same
-        rounding points as _forward_decode_gemv."""
+        bytes than bf16 at Q4_K).  Projections without a quantized copy use the bf16 GEMV
+        (quantized-blocks-only weights: the bf16 decode GEMM on the unpack scratch).  Same rounding
+        points as _forward_decode_gemv."""
         cfg, w = self.cfg, self.w
         B, eps = h.shape[0], cfg.rms_eps
         qs, ks = w.heads * cfg.head_dim, w.kv_heads * cfg.head_dim
@@ -1080,6 +1272,8 @@ class DecoderModel:
                 K.qgemv(h, ql["q"], out=qkv, ldo=ld)
                 K.qgemv(h, ql["k"], out=qkv[:, qs:], ldo=ld)
                 K.qgemv(h, ql["v"], out=qkv[:, qs + ks:], ldo=ld)
+            elif w.quant_only:
+                qkv = K.dgemm_linear(h, self._scratch_weight(i, "qkv"))
             else:
                 qkv = K.gemv(h, lw["qkv"])
             attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
@@ -1089,11 +1283,15 @@ class DecoderModel:
                 part = K._workspace(h.device, B * cfg.hidden)[:B * cfg.hidden].view(1, B, cfg.hidden)
                 K.qgemv(a2, ql["o"], "f32", out=part[0])
                 h = K.splitk_residual_rmsnorm(part, residual, lw["mlp_norm"], eps)
+            elif w.quant_only:
+                h = K.dgemm_residual_rmsnorm(a2, self._scratch_weight(i, "o"), residual, lw["mlp_norm"], eps)
             else:
                 h = K.gemv_residual_rmsnorm(a2, lw["o"], residual, lw["mlp_norm"], eps)
             g, u = ql["gate"], ql["up"]
             if g is not None and u is not None and g.qtype == u.qtype and fit_h:
                 a = K.qgemv(h, g, "swiglu", qw2=u)
+            elif w.quant_only:
+                a = K.dgemm_swiglu(h, self._scratch_weight(i, "gate_up"))
             else:
                 a = K.gemv(h, lw["gate_up"], "swiglu")
             nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
@@ -1101,6 +1299,8 @@ class DecoderModel:
                 part = K._workspace(h.device, B * cfg.hidden)[:B * cfg.hidden].view(1, B, cfg.hidden)
                 K.qgemv(a, ql["down"], "f32", out=part[0])
                 h = K.splitk_residual_rmsnorm(part, residual, nxt, eps)
+            elif w.quant_only:
+                h = K.dgemm_residual_rmsnorm(a, self._scratch_weight(i, "down"), residual, nxt, eps)
             else:
                 h = K.gemv_residual_rmsnorm(a, lw["down"], residual, nxt, eps)
         return h
@@ -1140,9 +1340,45 @@ class DecoderModel:
         torch.distributed.all_gather(parts, local, group=self.tp_group)
         return torch.cat(parts, -1)
 
+    def _quant_logits(self, hidden: torch.Tensor) -> torch.Tensor:
+        """Logits from ``q_lm_head`` alone (no bf16 head exists): the quantized GEMV up to 4 rows, the
+        quantized decode GEMM up to 128 -- what a bf16-resident model with CFC_DECODE_QGEMM=1 runs.
+        More rows: where that model runs its packed head on the bf16 decode GEMM (up to
+        DGEMM_MAX_ROWS), the same GEMM over the scratch, the head unpacked into it in row chunks of
+        whole tiles with the whole head's tile width and split, so the logits keep that model's
+        bits; past that (the library's range), the quantized decode GEMM in row slices of 128."""
+        qh = self.w.q_lm_head
+        B, Kd = hidden.shape
+        if B <= K.GEMV_MAX_M and qh.N % 4 == 0 and K.qgemv_fits(B, Kd):
+            return K.qgemv(hidden, qh)
+        if B <= K.QDGEMM_MAX_M:
+            return K.qdgemm(hidden, qh, "bf16")
+        out = torch.empty(B, qh.N, dtype=torch.bfloat16, device=hidden.device)
+        if B <= DGEMM_MAX_ROWS and qh.N % 64 == 0:
+            bn = K.dgemm_config(128, qh.N, Kd)[0]                  # pack_decode()'s tile width for the head
+            split = K.dgemm_config(B, qh.N, Kd, bn=bn)[1]          # dgemm_linear's split on the whole head
+            # dgemm.hip walks tile t's K / 64 stages starting at stage 37 t % (K / 64) (its K-order
+            # rotation): a chunk that starts at a multiple of K / 64 tiles gives every tile the start
+            # it has in the whole head, hence the same fp32 summation order.  (At split > 1 the start
+            # also depends on the tile count, so only the unsplit GEMM -- a head's 250+ tiles fill
+            # the chip without a split -- is chunked.)
+            period = bn * (Kd // 64)
+            step = self._scratch_data.numel() // Kd // period * period     # rows of the head the scratch holds
+            if split == 1 and step > 0:
+                for r0 in range(0, qh.N, step):
+                    n = min(step, qh.N - r0)
+                    pw = K.qunpack(qh.rows(r0, n), K.PackedWeight(self._scratch_data[:n * Kd], n, Kd, bn))
+                    K.dgemm(hidden, pw, "bf16", out=out[:, r0:r0 + n])
+                return out
+        for s in range(0, B, K.QDGEMM_MAX_M):
+            K.qdgemm(hidden[s:s + K.QDGEMM_MAX_M], qh, "bf16", out=out[s:s + K.QDGEMM_MAX_M])
+        return out
+
     def _local_logits(self, hidden: torch.Tensor) -> torch.Tensor:
         """This rank's vocab shard of the logits [B, V / tp]."""
         head = self.w.lm_head
+        if head is None:      # quantized-blocks-only weights whose lm_head stayed quantized
+            return self._quant_logits(hidden.contiguous())
         if (self.decode_qgemv and self.w.q_lm_head is not None and hidden.is_cuda
                 and hidden.shape[0] <= K.GEMV_MAX_M and hidden.is_contiguous() and self.w.q_lm_head.N % 4 == 0
                 and K.qgemv_fits(hidden.shape[0], hidden.shape[1])):

@@ -926,6 +926,49 @@ def _planar(qtype: int, blocks):
     raise ValueError(f"ggml type {qtype} has no quantized GEMV layout")
 
 
+def _plane_bytes(qtype: int, N: int, K: int) -> list[int]:
+    """Bytes of each plane of :func:`_planar`'s layout for an [N, K] weight."""
+    if qtype == 8:
+        return [N * K, N * K // 16]
+    if qtype == 12:
+        return [N * K // 2, N * K // 16]
+    if qtype == 14:
+        return [N * K // 2, N * K // 4, N * K // 16, N * K // 128]
+    raise ValueError(f"ggml type {qtype} has no quantized GEMV layout")
+
+
+def _unplanar(qtype: int, planes, N: int, K: int):
+    """The inverse of :func:`_planar`: planes (numpy uint8, flat) -> ggml blocks [N, nb, size]."""
+    import numpy as np
+    from ..runtime import gguf as G
+    per, size = G.BLOCK[qtype]
+    nb = K // per
+    blocks = np.empty((N, nb, size), np.uint8)
+    if qtype == 8:
+        blocks[:, :, 2:34] = planes[0].reshape(N, nb, 32)
+        blocks[:, :, 0:2] = planes[1].reshape(N, nb, 2)
+        return blocks
+    nib = planes[0].reshape(N, -1, 16)
+    c = np.concatenate([nib & 0xF, nib >> 4], 2)                   # 32-weight chunks, low 4 bits
+    if qtype == 12:
+        q = c.reshape(N, nb, 256)
+        for j in range(4):
+            blocks[:, :, 16 + 32 * j:48 + 32 * j] = q[:, :, 64 * j:64 * j + 32] | (q[:, :, 64 * j + 32:64 * j + 64] << 4)
+        blocks[:, :, 0:16] = planes[1].reshape(N, nb, 16)
+        return blocks
+    hi = planes[1].reshape(N, -1, 2, 1, 4)                          # [chunk, half h, -, b]
+    top = (hi >> np.array([0, 2, 4, 6], np.uint8).reshape(1, 1, 1, 4, 1)) & 3     # [chunk, h, f, b]
+    q6 = (c | (top.reshape(N, -1, 32) << 4)).reshape(N, nb, 256)
+    for h in range(2):
+        a, b, cc, d = (q6[:, :, 128 * h + 32 * t:128 * h + 32 * t + 32] for t in range(4))
+        blocks[:, :, 64 * h:64 * h + 32] = (a & 0xF) | ((cc & 0xF) << 4)
+        blocks[:, :, 64 * h + 32:64 * h + 64] = (b & 0xF) | ((d & 0xF) << 4)
+        blocks[:, :, 128 + 32 * h:160 + 32 * h] = (a >> 4) | ((b >> 4) << 2) | ((cc >> 4) << 4) | ((d >> 4) << 6)
+    blocks[:, :, 192:208] = planes[2].reshape(N, nb, 16)
+    blocks[:, :, 208:210] = planes[3].reshape(N, nb, 2)
+    return blocks
+
+
 @dataclasses.dataclass
 class QWeight:
     """One ggml-quantized weight [N, K] in the planar GPU layout of csrc/kernels/quant.hip (see
@@ -989,6 +1032,27 @@ class QWeight:
         from ..runtime import gguf as G
         per, size = G.BLOCK[self.qtype]
         return self.N * self.K // per * size
+
+    def rows(self, r0: int, n: int) -> "QWeight":
+        """Rows [r0, r0 + n) as a QWeight over the same buffer (every plane is row-major, so a row
+        range is a pointer offset per plane; r0 * K % 256 == 0 keeps the 16-byte loads aligned)."""
+        if not (0 <= r0 and 0 < n and r0 + n <= self.N) or (r0 * self.K) % 256:
+            raise ValueError(f"rows [{r0}, {r0 + n}) of a [{self.N}, {self.K}] quantized weight")
+        per_row = [b // self.N for b in _plane_bytes(self.qtype, self.N, self.K)]
+        offs = [o + r0 * pr - r0 * per_row[0] for o, pr in zip(self.offs, per_row)]
+        offs += [0] * (len(self.offs) - len(offs))
+        return QWeight(self.qtype, n, self.K, self.buf[r0 * per_row[0]:], tuple(offs))
+
+    def to_rowmajor_bf16(self) -> torch.Tensor:
+        """The weight as a row-major bf16 [N, K] CPU tensor: the planes turned back into ggml
+        blocks (:func:`_unplanar`) and dequantized by runtime/gguf.py's formulas -- the values the
+        GPU kernels compute from the planes (the CPU oracle of qunpack; rowmajor_layer of a model
+        resident in its quantized blocks only)."""
+        from ..runtime import gguf as G
+        host = self.buf.cpu().numpy()
+        planes = [host[o:o + n] for o, n in zip(self.offs, _plane_bytes(self.qtype, self.N, self.K))]
+        raw = _unplanar(self.qtype, planes, self.N, self.K).reshape(-1)
+        return torch.from_numpy(G.dequantize(raw, self.qtype, (self.N, self.K))).to(torch.bfloat16)
 
 
 def llama_cpp_q4km_types(layers: int) -> list[dict]:
@@ -1188,6 +1252,51 @@ def qdgemm(x: torch.Tensor, qw: "QWeight", epi: str = "part", split: int | None 
                                ptr if epi == "part" else None, None if epi == "part" else ptr,
                                int(slab), int(out.stride(-2)), _stream(x)), "cfc_qdgemm")
     return out
+
+
+# ------------------------------------------ quantized blocks -> packed bf16 scratch (qunpack.hip)
+
+def qunpack_ok(qw, bn: int) -> bool:
+    """Weights the unpack kernel takes: Q8_0 / Q4_K / Q6_K, N % 16 == 0, K % 256 == 0, into a
+    destination packed for one of the decode GEMM's tile widths."""
+    return (isinstance(qw, QWeight) and qw.qtype in QGEMV_TYPES and bn in DGEMM_BNS
+            and qw.N > 0 and qw.N % 16 == 0 and qw.K > 0 and qw.K % 256 == 0)
+
+
+def qunpack(qw: "QWeight", dst: PackedWeight, row0: int = 0, interleave: str | None = None,
+            split: int = 0) -> PackedWeight:
+    """dequant(qw) as bf16 into rows [row0, row0 + N) of the packed weight ``dst`` (qunpack.hip), on
+    the current stream.  ``interleave`` "gate" / "up": the weight is one half of an 8-row interleaved
+    gate/up pair -- its row j goes to row row0 + 16 (j // 8) + j % 8 (+ 8 for up) of a 2 N row range
+    (interleave_gate_up's order).  q, k, v (any mix of types) fill one qkv weight in three calls,
+    gate and up one gate_up weight in two.  ``split``: K parts per 16-row tile (0: the kernel's
+    pick).  Returns ``dst``."""
+    if not isinstance(qw, QWeight) or not isinstance(dst, PackedWeight):
+        raise ValueError("qunpack: qw must be a QWeight and dst a PackedWeight")
+    if interleave not in (None, "gate", "up"):
+        raise ValueError(f"qunpack: interleave {interleave!r}: expected None, gate or up")
+    if not qunpack_ok(qw, dst.bn):
+        raise ValueError(f"qunpack: weight [{qw.N}, {qw.K}] type {qw.qtype} into bn={dst.bn} "
+                         f"(types {QGEMV_TYPES}, N % 16 == 0, K % 256 == 0, bn in {DGEMM_BNS})")
+    if dst.data.dtype != torch.bfloat16 or not dst.data.is_contiguous() or dst.data.data_ptr() % 16:
+        raise ValueError(f"qunpack: destination must be contiguous, 16-byte aligned bf16, got {dst.data.dtype}")
+    if not dst.data.is_cuda or dst.data.device != qw.buf.device:
+        raise ValueError(f"qunpack: weight on {qw.buf.device}, destination on {dst.data.device} (GPU only)")
+    if dst.K != qw.K or dst.N % dst.bn or dst.data.numel() != dst.N * dst.K:
+        raise ValueError(f"qunpack: destination [{dst.N}, {dst.K}] of {dst.data.numel()} values, bn={dst.bn}, "
+                         f"does not hold a K={qw.K} weight in whole {dst.bn}-row tiles")
+    if row0 < 0 or row0 % 16:
+        raise ValueError(f"qunpack: row0 {row0} must be a non-negative multiple of 16")
+    rows = 2 * qw.N if interleave else qw.N
+    if row0 + rows > dst.N:
+        raise ValueError(f"qunpack: rows [{row0}, {row0 + rows}) past the destination's {dst.N}")
+    if not 0 <= split <= qw.K // 256:
+        raise ValueError(f"qunpack: split {split} outside 0 .. K / 256 = {qw.K // 256}")
+    o = tuple(qw.offs) + (0,) * (4 - len(qw.offs))
+    check(kernels().cfc_qunpack(qw.buf.data_ptr(), qw.qtype, qw.N, qw.K, o[1], o[2], o[3], dst.data.data_ptr(),
+                                dst.N, row0, dst.bn, {None: 0, "gate": 1, "up": 2}[interleave], split,
+                                _stream(dst.data)), "cfc_qunpack")
+    return dst
 
 
 def dequant_bf16(raw, qtype: int, shape, device) -> torch.Tensor:

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import dataclasses
 import json
+import os
 import time
 from abc import ABC, abstractmethod
 
@@ -82,7 +83,7 @@ class HipLLMSummarizer(Summarizer):
                  kv_cache_tokens: int = 524288, device: str = "cuda", seed: int = 1234, tp_group=None,
                  tp_rank: int = 0, ignore_eos: bool = False, top_k: int = 40, top_p: float = 0.95,
                  min_p: float = 0.05, stop_sequences=("</s>", "\n\n\n"), weight_dtype: str = "bf16",
-                 kv_cache_dtype: str = "bf16", **_):
+                 kv_cache_dtype: str = "bf16", gguf_resident: str = "bf16", **_):
         from ..models.decoder import DecoderModel, DecoderWeights, get_config, load_config_json
         from ..runtime.engine import LLMEngine
         from ..runtime.kv_cache import PagedKVCache
@@ -92,11 +93,16 @@ class HipLLMSummarizer(Summarizer):
             gguf_path, checkpoint_dir = checkpoint_dir, None
         if gguf_path:
             # llama.cpp / Ollama weights: bf16 copies for prefill and batches, the ggml blocks kept
-            # for the quantized B <= 4 decode GEMV (runtime/gguf.py, csrc/kernels/quant.hip)
+            # for the quantized B <= 4 decode GEMV (runtime/gguf.py, csrc/kernels/quant.hip).
+            # gguf_resident="quant" (LLM_GGUF_RESIDENT; CFC_GGUF_RESIDENT overrides): the ggml blocks
+            # ONLY -- Q4 files take Q4 memory, bf16 consumers read a scratch unpacked from the blocks
             from ..runtime import gguf as G
             if tensor_parallel > 1:
                 raise ValueError("GGUF checkpoints run on one GPU (tensor_parallel must be 1)")
-            w = DecoderWeights.from_gguf(gguf_path, dev)
+            resident = os.environ.get("CFC_GGUF_RESIDENT") or gguf_resident or "bf16"
+            if resident not in ("bf16", "quant"):
+                raise ValueError(f"gguf_resident / CFC_GGUF_RESIDENT = {resident!r}: expected bf16 or quant")
+            w = DecoderWeights.from_gguf(gguf_path, dev, resident=resident)
             cfg = w.cfg
             self.tokenizer = G.tokenizer_from_gguf(G.GGUFReader(gguf_path).metadata)
         elif checkpoint_dir:

@@ -15,6 +15,15 @@ over the batch); with quantized weights ``--ab-qgemm`` runs every point twice in
 on the quantized decode GEMM and with ``CFC_DECODE_QGEMM=0`` (the bf16 copies above B = 4).
 
     python scripts/bench_latency.py --models mistral-7b --weights q4_k_m --batch 8 --ab-qgemm
+
+``--gguf-resident quant`` keeps the quantized weights resident in their blocks only
+(DecoderWeights.to_quant_only: the bf16 consumers read a scratch unpacked from the blocks);
+``both`` runs every point on two weight sets of the same blocks in the same process, one resident
+each way, and every row carries resident_bytes() and torch.cuda.max_memory_allocated() (the
+process's peak since the weights were built: with ``both`` it covers the two weight sets, so run
+one residency per process to compare peaks).
+
+    python scripts/bench_latency.py --models mistral-7b --weights q4_k_m --batch 8 --gguf-resident both
 """
 import argparse
 import json
@@ -39,19 +48,34 @@ PUBLISHED = {
 }
 
 
-def run_model(name, prompt_lens, new, reps, seed, weights="bf16", batch=1, ab_qgemm=False):
+def run_model(name, prompt_lens, new, reps, seed, weights="bf16", batch=1, ab_qgemm=False, resident="bf16"):
     cfg = get_config(name)
     dev = torch.device("cuda")
-    w = DecoderWeights.random(cfg, dev, seed=seed)
     wbytes = cfg.num_params() * 2
+    if resident != "bf16" and weights == "bf16":
+        raise SystemExit("--gguf-resident quant / both needs --weights q4_k_m or q8_0")
+
+    def make_weights(quant_only):
+        w = DecoderWeights.random(cfg, dev, seed=seed)
+        if weights != "bf16":
+            # ggml-quantized projections (llama.cpp's Q4_K_M type recipe, or all Q8_0), random blocks:
+            # decode streams them (csrc/kernels/quant.hip); prefill keeps the bf16 copies unless the
+            # weights are resident in their blocks only (then it reads the unpack scratch)
+            from copilot_for_consensus_amd.ops.kernels import attach_random_quant
+            attach_random_quant(w, weights, seed)
+        return w.to_quant_only() if quant_only else w
+
+    # (weights, CFC_DECODE_QGEMM flag or None) per engine
+    runs = [(make_weights(r == "quant"), None) for r in (("bf16", "quant") if resident == "both" else (resident,))]
+    w = runs[0][0]
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()      # the peak from here on: resident weights + KV + activations
     if weights != "bf16":
-        # ggml-quantized projections (llama.cpp's Q4_K_M type recipe, or all Q8_0), random blocks:
-        # decode streams them (csrc/kernels/quant.hip); prefill keeps the bf16 copies
-        from copilot_for_consensus_amd.ops.kernels import attach_random_quant
-        attach_random_quant(w, weights, seed)
         wbytes = sum(q.nbytes for layer in w.qlayers for q in layer.values()) + w.q_lm_head.nbytes
+    if ab_qgemm and weights != "bf16":
+        runs = [(rw, flag) for rw, _ in runs for flag in (("1",) if rw.quant_only else ("1", "0"))]
     engines = []
-    for flag in (("1", "0") if ab_qgemm and weights != "bf16" else (None,)):
+    for w, flag in runs:
         saved = os.environ.get("CFC_DECODE_QGEMM")
         if flag is not None:
             os.environ["CFC_DECODE_QGEMM"] = flag
@@ -93,6 +117,10 @@ def run_model(name, prompt_lens, new, reps, seed, weights="bf16", batch=1, ab_qg
                 row["batch"] = batch
                 row["decode_path"] = eng.model.decode_path(batch)
             row["decode_qgemm"] = bool(eng.model.decode_qgemm)
+            if weights != "bf16":
+                row["gguf_resident"] = "quant" if eng.model.w.quant_only else "bf16"
+                row["resident_bytes"] = eng.model.w.resident_bytes()
+                row["max_memory_allocated"] = torch.cuda.max_memory_allocated()
             # HBM bytes one decode step must read: all weights + the KV of the context so far
             kv_bytes = 2 * cfg.layers * cfg.kv_heads * cfg.head_dim * 2 * (plen + new / 2)
             # (a batch shares the weight read: steps/s = tok/s / batch, every request's KV is read each step)
@@ -104,7 +132,7 @@ def run_model(name, prompt_lens, new, reps, seed, weights="bf16", batch=1, ab_qg
                 row["vs_published"] = round(row["decode_tok_s"] / pub["tok_s"], 2)
             print(json.dumps(row), flush=True)
             rows.append(row)
-    del engines, eng, kv, model
+    del engines, eng, kv, model, runs, w
     torch.cuda.empty_cache()
     return rows
 
@@ -121,9 +149,12 @@ def main():
     ap.add_argument("--batch", type=int, default=1, help="requests decoded together (decode tok/s: their sum)")
     ap.add_argument("--ab-qgemm", action="store_true",
                     help="quantized weights: every point also with CFC_DECODE_QGEMM=0, the two alternating")
+    ap.add_argument("--gguf-resident", choices=["bf16", "quant", "both"], default="bf16",
+                    help="quantized weights: keep the bf16 copies (bf16), the ggml blocks only (quant), or run "
+                         "every point on one weight set of each kind (both)")
     a = ap.parse_args()
     for name in a.models:
-        run_model(name, a.prompt, a.new, a.reps, a.seed, a.weights, a.batch, a.ab_qgemm)
+        run_model(name, a.prompt, a.new, a.reps, a.seed, a.weights, a.batch, a.ab_qgemm, a.gguf_resident)
 
 
 if __name__ == "__main__":
