@@ -53,6 +53,11 @@ _KERNEL_SIGS = {
     "cfc_sample": [P, I, I, F, c_uint32, P, P, P],
     "cfc_sample_truncated": [P, I, I, F, I, F, F, c_uint32, P, P, P],
     "cfc_decode_advance": [P, P, I, P, P, P, P, P, P, I, P, P, I, I] + [P] * 6 + [I] * 4 + [P] * 4,
+    "cfc_logit_processors": [P, I, I, P, I, P, P, P, P, P, I] + [P] * 8,
+    "cfc_token_logprobs": [P, P, I, I, I, P, P, P, I, P, P, P, P],
+    "cfc_logit_window_cap": [],
+    "cfc_logit_bias_cap": [],
+    "cfc_top_logprobs_cap": [],
     "cfc_knn_scores": [P, P, I, I, I, P, P, P, P],
     "cfc_topk_pass": [P, P, I, I, I, I, P, P, P],
     "cfc_knn_topk": [P, P, I, I, I, I, P, P, P, I, P, P, P],

@@ -1432,10 +1432,21 @@ class SamplingParams:
     top_k: int = 0
     top_p: float = 1.0
     min_p: float = 0.0
+    # the step also runs the logit processors (logit_bias, repeat / frequency / presence penalties
+    # from a LogitState) before this chain
+    processors: bool = False
+    # token log-probabilities recorded per step: -1 off, 0 the chosen token only, else the chosen
+    # token and the N most probable (N <= TOP_LOGPROBS_MAX)
+    logprobs: int = -1
 
     @classmethod
     def of(cls, t) -> "SamplingParams":
         return t if isinstance(t, SamplingParams) else cls(float(t))
+
+    @property
+    def logit_state(self) -> bool:
+        """Whether the step needs a :class:`LogitState` (either new kernel is in it)."""
+        return self.processors or self.logprobs >= 0
 
     @property
     def truncated(self) -> bool:
@@ -1467,6 +1478,266 @@ def sample(logits, out_ids, temperature=0.0, seed=0, step=None):
     check(kernels().cfc_sample(logits.data_ptr(), B, V, float(sp.temperature), int(seed) & 0xFFFFFFFF, _p(step),
                                out_ids.data_ptr(), _stream(logits)), "cfc_sample")
     return out_ids
+
+
+PENALTY_WINDOW_MAX = 1024   # history tokens kept per row for the penalties (logits.hip: PEN_WINDOW_CAP)
+LOGIT_BIAS_MAX = 512        # logit_bias entries per row (logits.hip: BIAS_CAP)
+TOP_LOGPROBS_MAX = 20       # top log-probabilities per record (logits.hip: TOPLP_CAP)
+
+
+@dataclasses.dataclass(frozen=True)
+class LogitParams:
+    """One row's logit processors, applied in llama.cpp's order before the sampling chain:
+    ``logit_bias`` ({id: bias}; ``False`` / -inf bans the token), then the repeat / frequency /
+    presence penalties over the last ``repeat_last_n`` tokens of the row's history (0: none,
+    negative: as much as the engine keeps).  ``penalize_prompt``: the history starts with the
+    prompt's tail (llama.cpp, Ollama) instead of the generated text only (OpenAI)."""
+    repeat_penalty: float = 1.0
+    repeat_last_n: int = 64
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: tuple = ()          # ((id, bias), ...), unique ids
+    penalize_prompt: bool = True
+
+    @classmethod
+    def make(cls, repeat_penalty=1.0, repeat_last_n=64, presence_penalty=0.0, frequency_penalty=0.0,
+             logit_bias=None, penalize_prompt=True, vocab: int | None = None) -> "LogitParams":
+        if not float(repeat_penalty) > 0:
+            raise ValueError("repeat_penalty must be positive")
+        items = logit_bias.items() if isinstance(logit_bias, dict) else (logit_bias or ())
+        bias: dict[int, float] = {}
+        for i, v in items:                       # the last entry of an id wins
+            v = -math.inf if v is False else float(v)
+            if math.isnan(v) or v == math.inf:
+                raise ValueError("logit_bias: a bias must be a finite number, -inf or false")
+            bias.pop(int(i), None)
+            bias[int(i)] = v
+        if len(bias) > LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias: more than {LOGIT_BIAS_MAX} entries")
+        if vocab is not None and any(not 0 <= i < vocab for i in bias):
+            raise ValueError(f"logit_bias: token id outside the vocabulary [0, {vocab})")
+        return cls(float(repeat_penalty), int(repeat_last_n), float(presence_penalty), float(frequency_penalty),
+                   tuple(bias.items()), bool(penalize_prompt))
+
+    @property
+    def penalised(self) -> bool:
+        return (self.repeat_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0) \
+            and self.repeat_last_n != 0
+
+    @property
+    def neutral(self) -> bool:
+        return not self.penalised and not self.logit_bias
+
+
+class LogitState:
+    """Per-row inputs of :func:`logit_processors` and records of :func:`token_logprobs` in
+    persistent tensors: a captured decode graph holds their pointers (as it does with the stop
+    strings' state), the host rewrites a row's values when a request takes the row.  ``window``:
+    history tokens kept per row for the penalties (<= PENALTY_WINDOW_MAX); ``rec_cap`` > 0: room
+    for that many log-probability records per row, each with ``top_n`` top entries."""
+
+    def __init__(self, B: int, device, window: int = PENALTY_WINDOW_MAX, rec_cap: int = 0, top_n: int = 0):
+        if not 1 <= int(window) <= PENALTY_WINDOW_MAX:
+            raise ValueError(f"penalty window must be in [1, {PENALTY_WINDOW_MAX}]")
+        if not 0 <= int(top_n) <= TOP_LOGPROBS_MAX:
+            raise ValueError(f"top log-probabilities must be in [0, {TOP_LOGPROBS_MAX}]")
+        self.B, self.window, self.rec_cap, self.top_n = int(B), int(window), int(rec_cap), int(top_n)
+        i32 = dict(dtype=torch.int32, device=device)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.prompt_tail = torch.zeros(B, self.window, **i32)
+        self.tail_len = torch.zeros(B, **i32)
+        self.last_n = torch.zeros(B, **i32)
+        self.repeat = torch.ones(B, **f32)
+        self.frequency = torch.zeros(B, **f32)
+        self.presence = torch.zeros(B, **f32)
+        self.bias_ids = torch.zeros(B, LOGIT_BIAS_MAX, **i32)
+        self.bias_vals = torch.zeros(B, LOGIT_BIAS_MAX, **f32)
+        self.n_bias = torch.zeros(B, **i32)
+        self.lp = self.top_ids = self.top_lp = None
+        if self.rec_cap > 0:
+            self.lp = torch.zeros(B, self.rec_cap, **f32)
+            self.top_ids = torch.zeros(B, self.rec_cap, max(1, self.top_n), **i32)
+            self.top_lp = torch.zeros(B, self.rec_cap, max(1, self.top_n), **f32)
+        self._work = None
+
+    _ROW_FIELDS = ("prompt_tail", "tail_len", "last_n", "repeat", "frequency", "presence", "bias_ids", "bias_vals",
+                   "n_bias", "lp", "top_ids", "top_lp")
+
+    def view(self, W: int) -> "LogitState":
+        """The first ``W`` rows (same storage): the continuous engine's narrower decode widths."""
+        if W == self.B:
+            return self
+        v = object.__new__(LogitState)
+        v.B, v.window, v.rec_cap, v.top_n, v._work = W, self.window, self.rec_cap, self.top_n, None
+        for f in self._ROW_FIELDS:
+            t = getattr(self, f)
+            setattr(v, f, None if t is None else t[:W])
+        v._parent = self
+        return v
+
+    def work(self, logits: torch.Tensor) -> torch.Tensor:
+        """One persistent [B, V] buffer: the processors' copy of the logits when the raw ones are
+        still needed for the log-probabilities."""
+        owner = getattr(self, "_parent", self)
+        w = owner._work
+        if w is None or w.shape[1] != logits.shape[1] or w.dtype != logits.dtype:
+            w = owner._work = torch.empty(owner.B, logits.shape[1], dtype=logits.dtype, device=logits.device)
+        return w[:logits.shape[0]]
+
+    def set_rows(self, rows, params, prompts) -> None:
+        """Install ``params[i]`` (LogitParams) for row ``rows[i]``: every field of the row is
+        rewritten, so nothing of its previous occupant remains.  The prompt tail is the last
+        ``min(repeat_last_n, window)`` tokens of ``prompts[i]``, or none."""
+        rows = list(rows)
+        n = len(rows)
+        if n == 0:
+            return
+        tail = torch.zeros(n, self.window, dtype=torch.int32)
+        bi = torch.zeros(n, LOGIT_BIAS_MAX, dtype=torch.int32)
+        bv = torch.zeros(n, LOGIT_BIAS_MAX, dtype=torch.float32)
+        ints = torch.zeros(n, 3, dtype=torch.int32)      # tail_len, last_n, n_bias
+        flt = torch.zeros(n, 3, dtype=torch.float32)     # repeat, frequency, presence
+        for i, (p, prompt) in enumerate(zip(params, prompts)):
+            t = ref.penalty_window(prompt, p.repeat_last_n, self.window) if p.penalised and p.penalize_prompt else []
+            if t:
+                tail[i, :len(t)] = torch.tensor(t, dtype=torch.int32)
+            if p.logit_bias:
+                if len(p.logit_bias) > LOGIT_BIAS_MAX:
+                    raise ValueError(f"logit_bias: more than {LOGIT_BIAS_MAX} entries")
+                bi[i, :len(p.logit_bias)] = torch.tensor([k for k, _ in p.logit_bias], dtype=torch.int32)
+                bv[i, :len(p.logit_bias)] = torch.tensor([v for _, v in p.logit_bias], dtype=torch.float32)
+            ints[i] = torch.tensor([len(t), p.repeat_last_n, len(p.logit_bias)], dtype=torch.int32)
+            flt[i] = torch.tensor([p.repeat_penalty, p.frequency_penalty, p.presence_penalty], dtype=torch.float32)
+        dev = self.tail_len.device
+        idx = torch.tensor(rows, dtype=torch.long, device=dev)
+        self.prompt_tail.index_copy_(0, idx, tail.to(dev))
+        self.bias_ids.index_copy_(0, idx, bi.to(dev))
+        self.bias_vals.index_copy_(0, idx, bv.to(dev))
+        ints, flt = ints.to(dev), flt.to(dev)
+        for j, dst in enumerate((self.tail_len, self.last_n, self.n_bias)):
+            dst.index_copy_(0, idx, ints[:, j].contiguous())
+        for j, dst in enumerate((self.repeat, self.frequency, self.presence)):
+            dst.index_copy_(0, idx, flt[:, j].contiguous())
+
+    def records(self, rows, counts) -> list:
+        """Host copy of the first ``counts[i]`` records of ``rows[i]``:
+        per row a list of (chosen logprob, [(id, logprob), ...])."""
+        rows = list(rows)
+        if self.lp is None or not rows:
+            return [None for _ in rows]
+        idx = torch.tensor(rows, dtype=torch.long, device=self.lp.device)
+        lp = self.lp.index_select(0, idx).cpu()
+        ids = self.top_ids.index_select(0, idx).cpu()
+        top = self.top_lp.index_select(0, idx).cpu()
+        out = []
+        for i, c in enumerate(counts):
+            c = min(int(c), self.rec_cap)
+            li, ii, ti = lp[i, :c].tolist(), ids[i, :c, :self.top_n].tolist(), top[i, :c, :self.top_n].tolist()
+            out.append([(li[j], [(a, b) for a, b in zip(ii[j], ti[j]) if a >= 0]) for j in range(c)])
+        return out
+
+
+@dataclasses.dataclass
+class LogitCtx:
+    """What one step hands the two kernels: the rows' state and where the step's generated tokens
+    and their count live -- ``step`` (static engine, one counter) or ``gen`` (continuous engine,
+    per row); neither: nothing generated yet (the prefill's first token, record 0)."""
+    state: LogitState
+    tokens: torch.Tensor | None = None
+    step: torch.Tensor | None = None
+    gen: torch.Tensor | None = None
+    done: torch.Tensor | None = None
+
+
+def _count_args(ctx: LogitCtx):
+    if ctx.step is not None and ctx.gen is not None:
+        raise ValueError("step and gen are exclusive")
+    for t, name in ((ctx.tokens, "tokens"), (ctx.step, "step"), (ctx.gen, "gen"), (ctx.done, "done")):
+        if t is not None:
+            _req(t, torch.int32, name)
+
+
+def logit_processors(logits: torch.Tensor, ctx: LogitCtx) -> torch.Tensor:
+    """logit_bias, then repeat / frequency / presence penalties, in place on ``logits`` [B, V]
+    (:func:`reference.logit_processors` defines the arithmetic).  The history of row b is its
+    prompt tail in ``ctx.state`` followed by ``ctx.tokens[b, :count]``.  Graph-capturable: no host
+    sync, no allocation; rows with ``ctx.done[b] != 0`` are left alone."""
+    s = ctx.state
+    B, V = logits.shape
+    if s.B != B:
+        raise ValueError(f"logit state has {s.B} rows, logits {B}")
+    _count_args(ctx)
+    if not logits.is_cuda:
+        n_bias = s.n_bias.tolist()
+        if max(n_bias, default=0) > LOGIT_BIAS_MAX:
+            raise ValueError(f"n_bias above {LOGIT_BIAS_MAX}")
+        hist, bias = [], []
+        for b in range(B):
+            cnt = 0 if ctx.tokens is None else int(ctx.gen[b]) if ctx.gen is not None else \
+                int(ctx.step[0]) if ctx.step is not None else 0
+            cnt = max(0, min(cnt, ctx.tokens.shape[1])) if ctx.tokens is not None else 0
+            h = s.prompt_tail[b, :int(s.tail_len[b])].tolist()
+            hist.append(h + (ctx.tokens[b, :cnt].tolist() if cnt else []))
+            ids = s.bias_ids[b, :n_bias[b]].tolist()
+            if any(not 0 <= i < V for i in ids):
+                raise ValueError(f"logit_bias: token id outside the vocabulary [0, {V})")
+            bias.append(list(zip(ids, s.bias_vals[b, :n_bias[b]].tolist())))
+        out = ref.logit_processors(logits, hist, s.last_n.tolist(), s.repeat.tolist(), s.frequency.tolist(),
+                                   s.presence.tolist(), bias, s.window)
+        if ctx.done is not None:
+            keep = ctx.done != 0
+            out[keep] = logits[keep]
+        logits.copy_(out)
+        return logits
+    _req(logits, torch.bfloat16, "logits")
+    for t, dt, name in ((s.prompt_tail, torch.int32, "prompt_tail"), (s.tail_len, torch.int32, "tail_len"),
+                        (s.last_n, torch.int32, "last_n"), (s.repeat, torch.float32, "repeat"),
+                        (s.frequency, torch.float32, "frequency"), (s.presence, torch.float32, "presence"),
+                        (s.bias_ids, torch.int32, "bias_ids"), (s.bias_vals, torch.float32, "bias_vals"),
+                        (s.n_bias, torch.int32, "n_bias")):
+        _req(t, dt, name)
+    if s.bias_ids.shape[1] != LOGIT_BIAS_MAX or s.prompt_tail.shape[1] != s.window:
+        raise ValueError("logit state: bias / prompt tail width")
+    check(kernels().cfc_logit_processors(
+        logits.data_ptr(), B, V, _p(ctx.tokens), ctx.tokens.shape[1] if ctx.tokens is not None else 0, _p(ctx.step),
+        _p(ctx.gen), _p(ctx.done), s.prompt_tail.data_ptr(), s.tail_len.data_ptr(), s.window, s.last_n.data_ptr(),
+        s.repeat.data_ptr(), s.frequency.data_ptr(), s.presence.data_ptr(), s.bias_ids.data_ptr(),
+        s.bias_vals.data_ptr(), s.n_bias.data_ptr(), _stream(logits)), "cfc_logit_processors")
+    return logits
+
+
+def token_logprobs(logits: torch.Tensor, chosen: torch.Tensor, ctx: LogitCtx, n: int) -> None:
+    """log_softmax of the raw ``logits`` [B, V] at ``chosen`` [B] and at the ``n`` most probable
+    tokens (value descending, ties by ascending id), written to record ``gen[b]`` / ``step`` (0
+    without either) of ``ctx.state``'s buffers; rows with ``done[b] != 0`` or a record index at or
+    past the capacity write nothing.  Graph-capturable."""
+    s = ctx.state
+    B, V = logits.shape
+    if not 0 <= n <= TOP_LOGPROBS_MAX:
+        raise ValueError(f"top logprobs must be in [0, {TOP_LOGPROBS_MAX}]")
+    if s.lp is None or n > s.top_n or s.B != B:
+        raise ValueError("logit state has no room for these records")
+    _count_args(ctx)
+    _req(chosen, torch.int32, "chosen")
+    if not logits.is_cuda:
+        lp, ids, top = ref.token_logprobs(logits, chosen, n)
+        for b in range(B):
+            r = int(ctx.gen[b]) if ctx.gen is not None else int(ctx.step[0]) if ctx.step is not None else 0
+            if (ctx.done is not None and int(ctx.done[b])) or not 0 <= r < s.rec_cap:
+                continue
+            s.lp[b, r] = lp[b]
+            s.top_ids[b, r, :n] = ids[b]
+            s.top_lp[b, r, :n] = top[b]
+        return
+    _req(logits, torch.bfloat16, "logits")
+    for t, dt, name in ((s.lp, torch.float32, "lp"), (s.top_ids, torch.int32, "top_ids"),
+                        (s.top_lp, torch.float32, "top_lp")):
+        _req(t, dt, name)
+    if n > 0 and s.top_ids.shape[2] != n:
+        raise ValueError("logit state: records hold another number of top entries")
+    check(kernels().cfc_token_logprobs(logits.data_ptr(), chosen.data_ptr(), B, V, n, _p(ctx.step), _p(ctx.gen),
+                                       _p(ctx.done), s.rec_cap, s.lp.data_ptr(), s.top_ids.data_ptr(),
+                                       s.top_lp.data_ptr(), _stream(logits)), "cfc_token_logprobs")
 
 
 def _stop_args(stop_state):

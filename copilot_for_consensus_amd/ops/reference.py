@@ -273,6 +273,64 @@ def sample_truncated(logits, temperature, top_k, top_p, min_p, generator=None, c
     return torch.tensor(out, dtype=torch.int32)
 
 
+def penalty_window(history, last_n: int, window_max: int) -> list[int]:
+    """The tokens a row's penalties see: the last ``last_n`` of its history (prompt tail ++
+    generated); 0 = none, negative or above ``window_max`` = as much as is kept."""
+    n = window_max if last_n < 0 or last_n > window_max else last_n
+    return list(history)[-n:] if n > 0 else []
+
+
+def logit_processors(logits, history, last_n, repeat, frequency, presence, bias=None, window_max: int = 1024):
+    """llama.cpp's sampler-chain order on every row of ``logits`` [B, V], fp32 math, one rounding
+    back to the logits' dtype per touched logit (untouched ones keep their bits):
+
+      1. ``bias[b]`` = [(id, value), ...] (unique ids): x[id] += value; -inf sets x[id] = -inf;
+      2. for every token t occurring c > 0 times in the row's window (:func:`penalty_window` of
+         ``history[b]``): x[t] = x[t] * repeat if x[t] <= 0 else x[t] / repeat, then
+         x[t] -= c * frequency + presence.
+
+    ``last_n`` / ``repeat`` / ``frequency`` / ``presence`` are per-row sequences.  Returns a new tensor."""
+    out = logits.clone()
+    f32 = torch.float32
+    for b in range(logits.shape[0]):
+        x = {}
+        for i, v in (bias[b] if bias is not None else ()):
+            i = int(i)
+            cur = x.get(i, logits[b, i].to(f32))
+            x[i] = torch.tensor(-math.inf, dtype=f32) if v == -math.inf else cur + torch.tensor(float(v), dtype=f32)
+        rep, fr, pr = (torch.tensor(float(t[b]), dtype=f32) for t in (repeat, frequency, presence))
+        if not (float(rep) == 1.0 and float(fr) == 0.0 and float(pr) == 0.0):
+            counts: dict[int, int] = {}
+            for t in penalty_window(history[b], int(last_n[b]), window_max):
+                t = int(t)
+                if 0 <= t < logits.shape[1]:
+                    counts[t] = counts.get(t, 0) + 1
+            for t, c in counts.items():
+                v = x.get(t, logits[b, t].to(f32))
+                v = v * rep if float(v) <= 0 else v / rep
+                x[t] = v - (torch.tensor(float(c), dtype=f32) * fr + pr)
+        for i, v in x.items():
+            out[b, i] = v.to(logits.dtype)
+    return out
+
+
+def token_logprobs(logits, chosen, n: int):
+    """fp32 log_softmax of the raw logits (NaN ranked as -inf, as the samplers): the chosen
+    token's value [B], and the ``n`` most probable tokens' ids [B, n] (int32) and values [B, n],
+    ordered by value descending, ties by ascending id (the order of :func:`sample_truncated`)."""
+    x = torch.nan_to_num(logits.float(), nan=-math.inf, posinf=math.inf, neginf=-math.inf)
+    lsm = torch.log_softmax(x, -1)
+    B, V = x.shape
+    lp = lsm.gather(1, chosen.long().view(B, 1))[:, 0]
+    k = min(n, V)
+    _, idx = torch.sort(x, dim=-1, descending=True, stable=True)
+    ids = torch.full((B, n), -1, dtype=torch.int32)
+    top = torch.full((B, n), -math.inf, dtype=torch.float32)
+    ids[:, :k] = idx[:, :k].to(torch.int32)
+    top[:, :k] = lsm.gather(1, idx[:, :k])
+    return lp, ids, top
+
+
 def knn_scores(X, Q, xnorm2=None, qnorm2=None):
     dots = Q.float() @ X.float().T
     if xnorm2 is None:

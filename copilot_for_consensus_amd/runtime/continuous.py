@@ -52,6 +52,9 @@ class Request:
     tokens: list[int] | None = None
     slot: int | None = None              # decode slot while running
     cancelled: bool = False
+    logit: object = None                 # ops.kernels.LogitParams (engines built with processors)
+    n_logprobs: int = -1                 # top log-probabilities wanted per token (-1: none)
+    logprobs: list | None = None         # one (chosen logprob, [(id, logprob), ...]) per token
 
     @property
     def latency_s(self) -> float | None:
@@ -62,7 +65,12 @@ class ContinuousEngine:
     def __init__(self, engine, max_slots: int = 128, max_new_cap: int = 512, max_prompt: int = 4096,
                  steps_per_sync: int = 16, stop_ids: tuple[int, ...] = (), temperature: float = 0.0, seed: int = 0,
                  max_admit_tokens: int | None = None, min_admit: int = 1, max_wait_s: float = 0.5,
-                 stop_strings=None, bulk_admit_frac: float = 0.5, sync=None):
+                 stop_strings=None, bulk_admit_frac: float = 0.5, sync=None, processors: bool = False,
+                 logprobs: int = -1):
+        """``processors`` / ``logprobs``: whether the captured step carries the logit-processor
+        kernel / records each token's log-probability and the ``logprobs`` most probable tokens'
+        (-1: no records).  They are properties of the engine and its graph; the penalties, biases
+        and the number of top entries a request reads back are per request (:meth:`submit`)."""
         self.engine = engine
         # TP leader: called with each step's decision before any device work (see the module doc)
         self.sync = sync
@@ -75,6 +83,9 @@ class ContinuousEngine:
         self.steps_per_sync = max(1, int(steps_per_sync))
         self.stop_ids = tuple(int(s) for s in stop_ids)
         self.sampling = K.SamplingParams.of(temperature)
+        if processors or logprobs >= 0:
+            self.sampling = dataclasses.replace(self.sampling, processors=bool(processors) or self.sampling.processors,
+                                                logprobs=max(int(logprobs), self.sampling.logprobs))
         self.seed = int(seed)
         self.max_admit_tokens = max_admit_tokens or engine.max_prefill_tokens * 4
         # admission batching: prefill waits for `min_admit` queued threads (or the oldest waiting
@@ -110,6 +121,9 @@ class ContinuousEngine:
         # completes one, so the slot is freed and refilled instead of decoding to its limit
         self.stop_strings = stop_strings
         self.stop_state = stop_strings.new_state(B, dev) if stop_strings is not None else None
+        # rows of the logit processors' parameters and of the log-probability records: created with
+        # the first step that needs them (the server sets ``sampling`` after construction)
+        self.logit_state = None
         # decode width: a burst runs the captured step over the first W slots only (admission takes
         # the lowest free slot), W the smallest bucket holding every occupied slot -- one request
         # alone decodes at B = 1 on the GEMV path, not as 1 live row of a 128-row batched GEMM
@@ -134,12 +148,22 @@ class ContinuousEngine:
         self.admit_log: list[tuple] = []     # (admit time, requests, first arrival, last arrival), epoch s
 
     # ------------------------------------------------------------------ API
-    def submit(self, prompt: list[int], max_new: int) -> Request:
+    def submit(self, prompt: list[int], max_new: int, logprobs: int | None = None, **logit_kw) -> Request:
+        """``logit_kw``: repeat_penalty, repeat_last_n, presence_penalty, frequency_penalty,
+        logit_bias, penalize_prompt (ops.kernels.LogitParams) -- this request's own, beside other
+        requests' in the same captured step; ``logprobs`` = N: its result carries each token's
+        log-probability and the N most probable tokens'.  Both need an engine built with them."""
         if not prompt:
             raise ValueError("empty prompt")
         if len(prompt) > self.max_prompt or max_new > self.cap or max_new < 1:
             raise ValueError(f"prompt {len(prompt)} > {self.max_prompt} or max_new {max_new} outside [1, {self.cap}]")
-        r = Request(self._rid, list(prompt), int(max_new), time.perf_counter())
+        lp = K.LogitParams.make(**logit_kw, vocab=self.model.cfg.vocab_size)
+        if not lp.neutral and not self.sampling.processors:
+            raise ValueError("this engine was built without the logit processors")
+        n_lp = -1 if logprobs is None else int(logprobs)
+        if n_lp > self.sampling.logprobs:
+            raise ValueError(f"this engine records at most {self.sampling.logprobs} top logprobs")
+        r = Request(self._rid, list(prompt), int(max_new), time.perf_counter(), logit=lp, n_logprobs=n_lp)
         self._rid += 1
         self.queue.append(r)
         return r
@@ -178,7 +202,25 @@ class ContinuousEngine:
                     row = row[:j]
                     break
             out[r.rid] = row
+        if self.sampling.logprobs >= 0 and self.logit_state is not None:
+            recs = self.logit_state.records([r.slot for r in live], [len(out[r.rid]) for r in live])
+            for r, rec in zip(live, recs):
+                r.logprobs = self._trim(r, rec)
         return out
+
+    @staticmethod
+    def _trim(r: Request, rec):
+        """A request's records: the top entries it asked for (none asked: no records)."""
+        if r.n_logprobs < 0 or rec is None:
+            return None
+        return [(lp, top[:r.n_logprobs]) for lp, top in rec]
+
+    def _logit_state(self):
+        if self.logit_state is None and self.sampling.logit_state:
+            n = self.sampling.logprobs
+            self.logit_state = K.LogitState(self.B, self.device, self.engine.penalty_window,
+                                            rec_cap=self.cap if n >= 0 else 0, top_n=max(0, n))
+        return self.logit_state
 
     @torch.inference_mode()
     def step(self) -> list[Request]:
@@ -285,7 +327,13 @@ class ContinuousEngine:
             take, tables, fresh, start = ([v[i] for i in order] for v in (take, tables, fresh, start))
         t = time.perf_counter()
         try:
-            first = self.engine._prefill([r.prompt for r in take], tables, self.sampling, self.seed, start)
+            ls, rec0 = self._logit_state(), {}
+            if ls is not None:
+                lps = [r.logit or K.LogitParams() for r in take]
+                first = self.engine._prefill([r.prompt for r in take], tables, self.sampling, self.seed, start,
+                                             lps, rec0)
+            else:
+                first = self.engine._prefill([r.prompt for r in take], tables, self.sampling, self.seed, start)
         except BaseException:
             # nothing was installed in a slot yet: return the blocks, put the requests back in front
             self.engine._release(tables, fresh, failed=True)
@@ -321,6 +369,13 @@ class ContinuousEngine:
         self.gen.index_fill_(0, idx, 1)
         if self.stop_state is not None:
             self.stop_state.set_slots(slots, sstates)
+        if ls is not None:
+            # every field of the slot's rows is rewritten: nothing of the previous occupant stays
+            ls.set_rows(slots, lps, [r.prompt for r in take])
+            for i, (lp0, ids0, top0) in rec0.items():
+                ls.lp[slots[i], 0] = lp0[0]
+                ls.top_ids[slots[i], 0] = ids0[0]
+                ls.top_lp[slots[i], 0] = top0[0]
         self.tokens.index_copy_(0, idx, torch.nn.functional.pad(rows_t[:, :1], (0, self.cap - 1)))
         self.stats["admitted"] += len(take)
         # admission timeline (wall clock): when, how many, first / last arrival of the admitted requests
@@ -338,7 +393,11 @@ class ContinuousEngine:
         hidden = self.model.forward_decode(self.ids[:W], self.positions[:W], self.slots[:W], self.ctx_lens[:W],
                                            self.block_tables[:W], self.kv, attn_workspace=self.workspace,
                                            part_blocks=self._pb[W], shared_blocks=self.shared)
-        self.engine._next_tokens(hidden, self.next_ids[:W], self.sampling, self.seed, self.step_t)
+        if self.sampling.logit_state:
+            ctx = K.LogitCtx(self._logit_state().view(W), tokens=self.tokens[:W], gen=self.gen[:W], done=self.done[:W])
+            self.engine._next_tokens(hidden, self.next_ids[:W], self.sampling, self.seed, self.step_t, ctx)
+        else:
+            self.engine._next_tokens(hidden, self.next_ids[:W], self.sampling, self.seed, self.step_t)
         K.decode_advance_cb(self.next_ids[:W], self.tokens[:W], self.gen[:W], self.limit[:W], self.ids[:W],
                             self.positions[:W], self.ctx_lens[:W], self.slots[:W], self.block_tables[:W],
                             self.done[:W], self.stop_t, ss)
@@ -388,13 +447,21 @@ class ContinuousEngine:
         now = time.perf_counter()
         stop = set(self.stop_ids)
         out = []
+        rows = []
         for i, s in enumerate(fin):
             row = toks[i, :min(gen[i], self.cap)].tolist()
             for j, t in enumerate(row):
                 if t in stop:
                     row = row[:j]
                     break
+            rows.append(row)
+        recs = [None] * len(fin)
+        if self.sampling.logprobs >= 0 and self.logit_state is not None:
+            recs = self.logit_state.records(fin, [len(row) for row in rows])
+        for i, s in enumerate(fin):
+            row = rows[i]
             r = self.slot_req[s]
+            r.logprobs = self._trim(r, recs[i])
             r.tokens, r.finished_s, r.slot = row, now, None
             out.append(r)
             self._release_slot(s)

@@ -39,6 +39,8 @@ class GenerationResult:
     ttft_s: float = 0.0
     decode_steps: int = 0
     cached_prompt_tokens: int = 0    # prompt tokens served from the prefix cache
+    # per sequence, one (chosen logprob, [(id, logprob), ...]) per returned token; None when off
+    logprobs: list | None = None
 
     @property
     def total_s(self) -> float:
@@ -63,6 +65,7 @@ class _Job:
     prefill_s: float
     ready: object = None          # event recorded after the state setup (stream handoff)
     order: list | None = None     # slot s holds caller prompt order[s] (longest-first slots)
+    logit: object = None          # ops.kernels.LogitParams of the batch (processors / logprobs on)
 
 
 class _DecodeState:
@@ -82,6 +85,7 @@ class _DecodeState:
         self.next_ids = torch.zeros(B, **i32)
         self.stop_ids = torch.zeros(0, **i32)
         self.stop_state = None     # runtime.stops.StopState when the request has stop strings
+        self.logit_state = None    # ops.kernels.LogitState when the step runs processors / logprobs
         self.workspace = torch.empty(max(1, n_part_ws), dtype=torch.float32, device=device)
         self.graph = None
 
@@ -93,7 +97,14 @@ class _DecodeState:
 
 class LLMEngine:
     def __init__(self, model, kv: PagedKVCache, max_prefill_tokens: int = 16384, use_graph: bool = True,
-                 stop_check_interval: int = 64, prefix_cache: bool | None = None):
+                 stop_check_interval: int = 64, prefix_cache: bool | None = None,
+                 penalty_window: int = K.PENALTY_WINDOW_MAX):
+        """``penalty_window``: history tokens kept per sequence for the repeat / frequency /
+        presence penalties (1 .. ops.kernels.PENALTY_WINDOW_MAX = 1024); a request's
+        ``repeat_last_n`` that is negative or larger means this many."""
+        if not 1 <= int(penalty_window) <= K.PENALTY_WINDOW_MAX:
+            raise ValueError(f"penalty_window must be in [1, {K.PENALTY_WINDOW_MAX}]")
+        self.penalty_window = int(penalty_window)
         self.model = model
         self.cfg = model.cfg
         self.kv = kv
@@ -168,10 +179,14 @@ class LLMEngine:
             print(f"[ar-debug] rank {ar.rank} {tag}: errors={ar.errors()} epochs[0:4]={ep[:4]} "
                   f"epochs[32]={ep[32]} key={ep[-1]} distinct={sorted(set(ep))[:6]}", flush=True)
 
-    def _prefill(self, prompts, tables, temperature, seed, start=None):
+    def _prefill(self, prompts, tables, temperature, seed, start=None, logit=None, records=None):
         """Chunked packed prefill; returns first sampled token per prompt.  ``start[s]`` tokens of
-        prompt s are already in the cache (shared prefix blocks)."""
+        prompt s are already in the cache (shared prefix blocks).  ``logit[s]`` (LogitParams, when
+        the sampling has processors / logprobs on): the first token gets the same treatment as the
+        decode steps' -- nothing generated yet, so its window is the prompt tail; its
+        log-probability record lands in ``records[s]`` = (lp [1], ids [1, N], top [1, N])."""
         n = len(prompts)
+        sp = K.SamplingParams.of(temperature)
         first_dev = torch.zeros(n, dtype=torch.int32, device=self.device)
         pos = list(start) if start is not None else [0] * n  # tokens of each prompt already in the cache
         order = list(range(n))
@@ -196,9 +211,22 @@ class LLMEngine:
             for (_, finishing, d_fin), hidden in zip(metas, hiddens):
                 if finishing:
                     out = torch.empty(len(finishing), dtype=torch.int32, device=self.device)
-                    self._next_tokens(hidden, out, temperature, seed,
-                                      torch.zeros(1, dtype=torch.int32, device=self.device))
+                    ctx = None
+                    if sp.logit_state:
+                        ls = K.LogitState(len(finishing), self.device, self.penalty_window,
+                                          rec_cap=1 if sp.logprobs >= 0 else 0, top_n=max(0, sp.logprobs))
+                        ls.set_rows(range(len(finishing)), [logit[s] for s in finishing],
+                                    [prompts[s] for s in finishing])
+                        ctx = K.LogitCtx(ls)
+                    step0 = torch.zeros(1, dtype=torch.int32, device=self.device)
+                    if ctx is None:
+                        self._next_tokens(hidden, out, temperature, seed, step0)
+                    else:
+                        self._next_tokens(hidden, out, temperature, seed, step0, ctx)
                     first_dev.index_copy_(0, d_fin.long(), out)
+                    if ctx is not None and sp.logprobs >= 0 and records is not None:
+                        for r, s in enumerate(finishing):
+                            records[s] = (ls.lp[r], ls.top_ids[r], ls.top_lp[r])
             for (s, _, b) in chunk:
                 pos[s] = b
             self.progress += 1
@@ -267,7 +295,9 @@ class LLMEngine:
         return t.pin_memory().to(self.device, non_blocking=True)
 
     def _tp_greedy(self, temperature) -> bool:
-        return getattr(self.model.w, "tp_size", 1) > 1 and K.SamplingParams.of(temperature).temperature <= 0
+        sp = K.SamplingParams.of(temperature)
+        # processors / logprobs need the whole row: the all-gathered-logits path of temperature > 0
+        return getattr(self.model.w, "tp_size", 1) > 1 and sp.temperature <= 0 and not sp.logit_state
 
     def _graph_for(self, B, temperature) -> bool:
         if not self.use_graph:
@@ -276,23 +306,48 @@ class LLMEngine:
             return self._tp_greedy(temperature) and self.model.graph_collectives_ok(B)
         return True
 
-    def _next_tokens(self, hidden, out, temperature, seed, step):
+    def _next_tokens(self, hidden, out, temperature, seed, step, logit=None):
         """Sample the next token of every row; TP greedy reduces (max, argmax) keys instead of
-        all-gathering the logits (DecoderModel.greedy_ids)."""
+        all-gathering the logits (DecoderModel.greedy_ids).  ``logit`` (ops.kernels.LogitCtx), with
+        ``processors`` / ``logprobs`` in the sampling parameters: raw logits -> processors (on a
+        copy when the raw ones are still needed) -> sample -> log-probability record of the raw
+        logits.  With neither on, the launches are the ones above and nothing else."""
         if self._tp_greedy(temperature):
             return self.model.greedy_ids(hidden, out)
-        return K.sample(self.model.logits(hidden), out, temperature, seed, step)
+        sp = K.SamplingParams.of(temperature)
+        if not sp.logit_state:
+            return K.sample(self.model.logits(hidden), out, temperature, seed, step)
+        if logit is None:
+            raise ValueError("processors / logprobs need a logit state")
+        raw = self.model.logits(hidden)
+        x = raw
+        if sp.processors:
+            if sp.logprobs >= 0:
+                x = logit.state.work(raw)
+                x.copy_(raw)
+            K.logit_processors(x, logit)
+        K.sample(x, out, sp, seed, step)
+        if sp.logprobs >= 0:
+            K.token_logprobs(raw, out, logit, sp.logprobs)
+        return out
 
     def _decode_step(self, st: _DecodeState, part_blocks, temperature, seed):
         hidden = self.model.forward_decode(st.ids, st.positions, st.slots, st.ctx_lens, st.block_tables, self.kv,
                                            attn_workspace=st.workspace, part_blocks=part_blocks,
                                            shared_blocks=st.shared)
-        self._next_tokens(hidden, st.next_ids, temperature, seed, st.step)
+        if st.logit_state is not None:
+            ctx = K.LogitCtx(st.logit_state, tokens=st.tokens, step=st.step, done=st.done)
+            self._next_tokens(hidden, st.next_ids, temperature, seed, st.step, ctx)
+        else:
+            self._next_tokens(hidden, st.next_ids, temperature, seed, st.step)
         K.decode_advance(st.next_ids, st.tokens, st.step, st.ids, st.positions, st.ctx_lens, st.slots,
                          st.block_tables, st.done, st.stop_ids, st.stop_state)
 
-    def _state(self, B, max_blocks, max_new, part_blocks, stop_ids, stop_strings=None, slot=0):
+    def _state(self, B, max_blocks, max_new, part_blocks, stop_ids, stop_strings=None, slot=0, sampling=None):
         key = (B, max_blocks, max_new, tuple(stop_ids), id(stop_strings) if stop_strings is not None else None, slot)
+        lkey = (sampling.processors, sampling.logprobs) if sampling is not None and sampling.logit_state else None
+        if lkey is not None:
+            key += (lkey,)
         st = self._states.get(key)
         if st is None:
             P = -part_blocks if part_blocks < 0 else math.ceil(max_blocks / part_blocks)
@@ -303,6 +358,9 @@ class LLMEngine:
             if stop_strings is not None:
                 st.stop_state = stop_strings.new_state(B, self.device)
                 st.stop_matcher = stop_strings      # keeps id(stop_strings) in the key valid
+            if lkey is not None:
+                st.logit_state = K.LogitState(B, self.device, self.penalty_window,
+                                              rec_cap=max_new if lkey[1] >= 0 else 0, top_n=max(0, lkey[1]))
             self._states[key] = st
         return st
 
@@ -336,16 +394,24 @@ class LLMEngine:
     @torch.inference_mode()
     def generate(self, prompts: list[list[int]], max_new_tokens: int, temperature: float = 0.0, seed: int = 0,
                  stop_ids: tuple[int, ...] = (), ignore_eos: bool = False, top_k: int = 0, top_p: float = 1.0,
-                 min_p: float = 0.0, stop_strings=None) -> GenerationResult:
+                 min_p: float = 0.0, stop_strings=None, repeat_penalty: float = 1.0, repeat_last_n: int = 64,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
+                 penalize_prompt: bool = True, logprobs: int | None = None) -> GenerationResult:
         """``temperature`` (or a :class:`ops.kernels.SamplingParams`) with optional top-k / top-p /
         min-p truncation -- all applied on device inside the captured decode step.
         ``stop_strings`` (runtime.stops.StopStringMatcher): a sequence finishes, on the device, at
         the token whose text completes a stop string; its tokens end with that token (the caller
-        cuts the text at the stop, as llama.cpp's server does)."""
+        cuts the text at the stop, as llama.cpp's server does).
+        ``repeat_penalty`` / ``repeat_last_n`` / ``presence_penalty`` / ``frequency_penalty`` /
+        ``logit_bias`` ({id: bias}, ``False`` bans) / ``penalize_prompt``: the logit processors of
+        :class:`ops.kernels.LogitParams`, for the whole batch.  ``logprobs`` = N >= 0: the result
+        carries each token's log-probability and the N most probable tokens' (of the raw logits)."""
         if top_k or top_p < 1.0 or min_p > 0.0:
             temperature = K.SamplingParams(float(temperature), int(top_k), float(top_p), float(min_p))
         else:
             temperature = K.SamplingParams.of(temperature)
+        temperature, logit = self._logit_args(temperature, repeat_penalty, repeat_last_n, presence_penalty,
+                                              frequency_penalty, logit_bias, penalize_prompt, logprobs)
         B = len(prompts)
         if B == 0:
             return GenerationResult([], [])
@@ -356,20 +422,36 @@ class LLMEngine:
         if ignore_eos:
             stop_ids = ()
         job = self.start(prompts, max_new_tokens, temperature, seed, stop_ids, stop_strings=stop_strings,
-                         _resolved=True)
+                         _resolved=True, _logit=logit)
         return self.finish(job)
+
+    def _logit_args(self, sampling, repeat_penalty=1.0, repeat_last_n=64, presence_penalty=0.0,
+                    frequency_penalty=0.0, logit_bias=None, penalize_prompt=True, logprobs=None):
+        """(SamplingParams, LogitParams | None) of a call's keyword arguments: the processors are
+        switched on by any non-neutral value (or by ``sampling.processors``), the records by
+        ``logprobs`` (or ``sampling.logprobs``); with neither, ``sampling`` is returned as it came."""
+        lp = K.LogitParams.make(repeat_penalty, repeat_last_n, presence_penalty, frequency_penalty, logit_bias,
+                                penalize_prompt, vocab=self.cfg.vocab_size)
+        n = sampling.logprobs if logprobs is None else int(logprobs)
+        if n > K.TOP_LOGPROBS_MAX:
+            raise ValueError(f"logprobs must be at most {K.TOP_LOGPROBS_MAX}")
+        proc = sampling.processors or not lp.neutral
+        if not proc and n < 0:
+            return sampling, None
+        return dataclasses.replace(sampling, processors=proc, logprobs=max(n, -1)), lp
 
     @torch.inference_mode()
     def start(self, prompts: list[list[int]], max_new_tokens: int, temperature=0.0, seed: int = 0,
               stop_ids: tuple[int, ...] = (), ignore_eos: bool = False, stop_strings=None, slot: int = 0,
-              stream_sync: bool = False, _resolved: bool = False) -> _Job:
+              stream_sync: bool = False, _resolved: bool = False, _logit=None, **logit_kw) -> _Job:
         """First half of :meth:`generate`: KV allocation, the chunked prefill and the decode state
         of the batch.  ``slot`` picks one of several decode states (and captured graphs) of the same
         shape, so a batch can be prefilled while another one decodes; ``stream_sync`` waits on the
         current stream only (not the device) -- the other batch's decode keeps running.  A
-        thread-safe pair with :meth:`finish` (allocation and release are serialised)."""
+        thread-safe pair with :meth:`finish` (allocation and release are serialised).
+        ``logit_kw``: the processor / logprobs keyword arguments of :meth:`generate`."""
         if not _resolved:
-            temperature = K.SamplingParams.of(temperature)
+            temperature, _logit = self._logit_args(K.SamplingParams.of(temperature), **logit_kw)
             if not ignore_eos and self.cfg.eos_id not in stop_ids:
                 stop_ids = tuple(stop_ids) + (self.cfg.eos_id,)
             if ignore_eos:
@@ -413,13 +495,25 @@ class LLMEngine:
             barrier()
             t0 = time.perf_counter()
             with span("llm.prefill"):
-                first = self._prefill(prompts, tables, temperature, seed, start)
+                if temperature.logit_state:
+                    if _logit is None:
+                        _logit = K.LogitParams()
+                    rec0: dict = {}
+                    first = self._prefill(prompts, tables, temperature, seed, start, [_logit] * B, rec0)
+                else:
+                    first = self._prefill(prompts, tables, temperature, seed, start)
             barrier()
             t1 = time.perf_counter()
             self._ar_trace(f"after prefill of {B} x {sum(lens)} tokens")
 
             part_blocks = self._part_blocks(B, max_blocks)
-            st = self._state(B, max_blocks, max_new_tokens, part_blocks, stop_ids, stop_strings, slot)
+            st = self._state(B, max_blocks, max_new_tokens, part_blocks, stop_ids, stop_strings, slot, temperature)
+            if st.logit_state is not None:
+                st.logit_state.set_rows(range(B), [_logit] * B, prompts)
+                for b, (lp0, ids0, top0) in rec0.items():
+                    st.logit_state.lp[b, 0] = lp0[0]
+                    st.logit_state.top_ids[b, 0] = ids0[0]
+                    st.logit_state.top_lp[b, 0] = top0[0]
             st.block_tables.zero_()
             bt = torch.zeros(B, max_blocks, dtype=torch.int32)
             for b, t in enumerate(tables):
@@ -459,7 +553,7 @@ class LLMEngine:
                 self._release(tables, fresh, failed=True)
             raise
         return _Job(st, tables, fresh, lens, start, B, max_new_tokens, tuple(stop_ids), stop_strings, part_blocks,
-                    temperature, seed, t1 - t0, ready, order)
+                    temperature, seed, t1 - t0, ready, order, _logit)
 
     @torch.inference_mode()
     def finish(self, job: _Job, switch=None) -> GenerationResult:
@@ -529,13 +623,17 @@ class LLMEngine:
                     break
             out.append(row)
         lens = job.lens
+        recs = None
+        if st.logit_state is not None and temperature.logprobs >= 0:
+            recs = st.logit_state.records(range(B), [len(row) for row in out])
         if job.order is not None:            # back to the caller's prompt order
             inv = [0] * B
             for slot, i in enumerate(job.order):
                 inv[i] = slot
             out, lens = [out[inv[i]] for i in range(B)], [lens[inv[i]] for i in range(B)]
+            recs = [recs[inv[i]] for i in range(B)] if recs is not None else None
         return GenerationResult(out, lens, prefill_s=job.prefill_s, decode_s=t2 - t1, ttft_s=job.prefill_s,
-                                decode_steps=steps, cached_prompt_tokens=sum(job.start))
+                                decode_steps=steps, cached_prompt_tokens=sum(job.start), logprobs=recs)
 
     def _release(self, tables, fresh, failed: bool = False):
         if self.prefix_cache is None:

@@ -65,6 +65,26 @@ class GenRequest:
     handle: Any = None                   # (engine key, continuous Request) while on a slot engine
     loop: Any = None                     # asyncio loop + event of an async waiter (the HTTP handlers)
     aevent: Any = None
+    # logit processors (ops.kernels.LogitParams) and token log-probabilities; the defaults are neutral / off
+    repeat_penalty: float = 1.0
+    repeat_last_n: int = 64
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Any = None               # {id: bias}; -inf bans the token
+    penalize_prompt: bool = True         # the penalty window starts in the prompt (llama.cpp, Ollama)
+    n_probs: int = -1                    # top log-probabilities per token; -1: no records
+    logprobs: Any = None                 # one (chosen logprob, [(id, logprob), ...]) per token of `tokens`
+
+    @property
+    def processors(self) -> bool:
+        penalised = (self.repeat_penalty != 1.0 or self.presence_penalty != 0.0 or
+                     self.frequency_penalty != 0.0) and self.repeat_last_n != 0
+        return penalised or bool(self.logit_bias)
+
+    def logit_kw(self) -> dict:
+        return dict(repeat_penalty=self.repeat_penalty, repeat_last_n=self.repeat_last_n,
+                    presence_penalty=self.presence_penalty, frequency_penalty=self.frequency_penalty,
+                    logit_bias=self.logit_bias, penalize_prompt=self.penalize_prompt)
 
     def complete(self) -> None:
         if self.stream and self.on_delta is not None and not self.error:
@@ -77,8 +97,13 @@ class GenRequest:
 
     def key(self):
         sampled = self.temperature > 0
-        return (round(self.temperature, 6), self.top_k if sampled else 0, round(self.top_p, 6) if sampled else 1.0,
-                round(self.min_p, 6) if sampled else 0.0, self.seed if sampled else 0, self.ignore_eos)
+        key = (round(self.temperature, 6), self.top_k if sampled else 0, round(self.top_p, 6) if sampled else 1.0,
+               round(self.min_p, 6) if sampled else 0.0, self.seed if sampled else 0, self.ignore_eos)
+        # whether the two logit kernels are in the captured step is the engine's; the penalty values,
+        # biases and the number of top entries are per request, so they are no part of the key
+        if self.processors or self.n_probs >= 0:
+            key += ((self.processors, self.n_probs >= 0),)
+        return key
 
 
 class BatchScheduler:
@@ -147,6 +172,9 @@ class BatchScheduler:
                                   seed=r.seed, max_wait_s=self.wait_s)
             ce.sampling = K.SamplingParams(r.temperature, r.top_k, r.top_p, r.min_p) if r.temperature > 0 \
                 else K.SamplingParams.of(0.0)
+            if r.processors or r.n_probs >= 0:
+                ce.sampling = dataclasses.replace(ce.sampling, processors=r.processors,
+                                                  logprobs=K.TOP_LOGPROBS_MAX if r.n_probs >= 0 else -1)
             self.engines[key] = ce
             self._inflight[key] = {}
         return ce
@@ -183,12 +211,21 @@ class BatchScheduler:
                 if ce is None:
                     legacy.setdefault(r.key(), []).append(r)
                 else:
-                    cr = ce.submit(r.prompt_ids, r.max_new)
+                    if r.processors or r.n_probs >= 0:
+                        cr = ce.submit(r.prompt_ids, r.max_new, logprobs=r.n_probs if r.n_probs >= 0 else None,
+                                       **r.logit_kw())
+                    else:
+                        cr = ce.submit(r.prompt_ids, r.max_new)
                     r.handle = (r.key(), cr)
                     self._inflight[r.key()][cr.rid] = r
             for g in legacy.values():
-                for s in range(0, len(g), self.max_batch):
-                    self._run(g[s:s + self.max_batch])
+                # generate() applies one set of penalties to its whole batch: such requests run alone
+                plain = [r for r in g if not (r.processors or r.n_probs >= 0)]
+                for r in g:
+                    if r.processors or r.n_probs >= 0:
+                        self._run([r])
+                for s in range(0, len(plain), self.max_batch):
+                    self._run(plain[s:s + self.max_batch])
             for key, ce in list(self.engines.items()):
                 if not ce.pending():
                     continue
@@ -208,6 +245,7 @@ class BatchScheduler:
                 self._stream_partials(key, ce, {cr.rid for cr in finished})
                 for cr in finished:
                     r = self._inflight[key].pop(cr.rid)
+                    r.logprobs = cr.logprobs
                     self._finish(r, cr.tokens, cr.tokens is not None and len(cr.tokens) >= r.max_new,
                                  (cr.first_token_s or cr.submitted_s) - cr.submitted_s,
                                  cr.finished_s - (cr.first_token_s or cr.submitted_s))
@@ -249,6 +287,8 @@ class BatchScheduler:
         else:
             r.finish = "length" if hit_limit else "stop"
         r.text, r.tokens = text, toks
+        if r.logprobs is not None:
+            r.logprobs = list(r.logprobs[:len(toks)])
         r.prompt_s, r.gen_s = prompt_s, gen_s
         self.served += 1
 
@@ -261,9 +301,15 @@ class BatchScheduler:
             return
         try:
             t0 = time.perf_counter()
+            extra = {}
+            if r0.processors or r0.n_probs >= 0:       # such a group is one request (see _loop)
+                extra = dict(r0.logit_kw(), logprobs=r0.n_probs if r0.n_probs >= 0 else None)
             res = self.engine.generate([r.prompt_ids for r in group], max(r.max_new for r in group),
                                        temperature=r0.temperature, seed=r0.seed, ignore_eos=r0.ignore_eos,
-                                       top_k=r0.top_k, top_p=r0.top_p, min_p=r0.min_p)
+                                       top_k=r0.top_k, top_p=r0.top_p, min_p=r0.min_p, **extra)
+            if res.logprobs is not None:
+                for r, rec in zip(group, res.logprobs):
+                    r.logprobs = rec
             dt = time.perf_counter() - t0
             self.batches += 1
             self.max_seen_batch = max(self.max_seen_batch, len(group))
@@ -320,6 +366,93 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
             raise HTTPException(400, "empty prompt")
         return ids
 
+    vocab = int(engine.cfg.vocab_size)
+
+    def bad(field: str, why: str):
+        raise HTTPException(400, f"{field}: {why}")
+
+    def number(field: str, v, default: float) -> float:
+        if v is None:
+            return default
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            bad(field, "must be a number")
+        return float(v)
+
+    def logit_fields(body: dict, *, bias_pairs: bool, last_n=64, penalize_prompt: bool = True, n_probs: int = -1,
+                     stream: bool = False, repeat: bool = True) -> dict:
+        """The request's logit processors and log-probability fields as GenRequest attributes; a
+        value this server cannot honour is refused by name (400), never dropped."""
+        from ..ops import kernels as K
+        out: dict[str, Any] = {"penalize_prompt": penalize_prompt, "n_probs": n_probs}
+        if repeat:
+            out["repeat_penalty"] = number("repeat_penalty", body.get("repeat_penalty"), 1.0)
+            if out["repeat_penalty"] <= 0:
+                bad("repeat_penalty", "must be positive")
+            n = number("repeat_last_n", body.get("repeat_last_n"), last_n)
+            if n != int(n):
+                bad("repeat_last_n", "must be an integer")
+            out["repeat_last_n"] = int(n)
+        else:
+            out["repeat_last_n"] = last_n
+        out["presence_penalty"] = number("presence_penalty", body.get("presence_penalty"), 0.0)
+        out["frequency_penalty"] = number("frequency_penalty", body.get("frequency_penalty"), 0.0)
+        raw = body.get("logit_bias")
+        if raw:
+            if bias_pairs:      # llama.cpp: [[id, bias | false], ...]
+                if not isinstance(raw, list) or any(not isinstance(e, (list, tuple)) or len(e) != 2 for e in raw):
+                    bad("logit_bias", "must be a list of [token id, bias] pairs")
+                items = [(e[0], e[1]) for e in raw]
+            else:               # OpenAI: {"id": bias}
+                if not isinstance(raw, dict):
+                    bad("logit_bias", "must be an object of token id -> bias")
+                items = list(raw.items())
+            if len(items) > K.LOGIT_BIAS_MAX:
+                bad("logit_bias", f"more than {K.LOGIT_BIAS_MAX} entries")
+            bias: dict[int, float] = {}
+            for i, v in items:
+                try:
+                    i = int(i)
+                except (TypeError, ValueError):
+                    bad("logit_bias", f"token id {i!r} is not an integer")
+                if not 0 <= i < vocab:
+                    bad("logit_bias", f"token id {i} is outside the vocabulary [0, {vocab})")
+                if v is False:
+                    v = float("-inf")
+                elif isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v == float("inf"):
+                    bad("logit_bias", f"bias of token {i} must be a number or false")
+                bias.pop(i, None)
+                bias[i] = float(v)
+            out["logit_bias"] = bias
+        if stream and n_probs >= 0:
+            bad("stream", "token log-probabilities are not streamed; ask for them with stream: false")
+        return out
+
+    def with_fields(r: GenRequest, fields: dict) -> GenRequest:
+        for k, v in fields.items():
+            setattr(r, k, v)
+        return r
+
+    def token_entries(r: GenRequest) -> list[dict]:
+        """One entry per returned token: its text piece (incremental decoding of the returned
+        tokens), where the piece starts in the text, and its record.  Entries stop where the
+        returned text stops -- at the stop-string cut."""
+        out, prev = [], ""
+        for i, (tok, rec) in enumerate(zip(r.tokens, r.logprobs or [])):
+            cur = tokenizer.decode(r.tokens[:i + 1])
+            start = min(len(prev), len(cur))
+            piece = cur[start:]
+            if r.stopping_word:
+                if start >= len(r.text):
+                    break
+                piece = piece[:len(r.text) - start]
+            out.append({"id": int(tok), "token": piece, "offset": start, "logprob": float(rec[0]),
+                        "top": [(int(a), tokenizer.decode([int(a)]), float(b)) for a, b in rec[1]]})
+            prev = cur
+        return out
+
+    def utf8(text: str) -> list[int]:
+        return list(text.encode("utf-8"))
+
     def prepare(prompt, n_predict, temperature, top_k, top_p, min_p, seed, stop, ignore_eos=False) -> GenRequest:
         ids = encode(prompt)
         want = None if n_predict is None or int(n_predict) < 0 else int(n_predict)
@@ -341,9 +474,9 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
         r.truncated = truncated
         return r
 
-    async def run(*args, **kw) -> GenRequest:
+    async def run(*args, fields: dict | None = None, **kw) -> GenRequest:
         try:
-            return await sched.asubmit(prepare(*args, **kw))
+            return await sched.asubmit(with_fields(prepare(*args, **kw), fields or {}))
         except RuntimeError as e:
             raise HTTPException(500, str(e))
 
@@ -404,14 +537,28 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
         args = (body.get("prompt"), body.get("n_predict", default_n_predict), body.get("temperature", 0.8),
                 body.get("top_k", 40), body.get("top_p", 0.95), body.get("min_p", 0.05), body.get("seed"),
                 body.get("stop"), body.get("ignore_eos", False))
+        n_probs = number("n_probs", body.get("n_probs"), 0)
+        # the window includes the prompt; n_probs 0 is "no probabilities", as in llama.cpp
+        fields = logit_fields(body, bias_pairs=True, n_probs=min(int(n_probs), 20) if n_probs > 0 else -1,
+                              stream=bool(body.get("stream")))
         if body.get("stream"):
-            return streamed(prepare(*args), lambda d: "data: " + json.dumps({"content": d, "stop": False}) + "\n\n",
+            return streamed(with_fields(prepare(*args), fields),
+                            lambda d: "data: " + json.dumps({"content": d, "stop": False}) + "\n\n",
                             lambda r: "data: " + json.dumps({**llama_record(r), "content": ""} if r else
                                                             {"error": "generation failed", "stop": True}) + "\n\n",
                             "text/event-stream")
-        return llama_record(await run(*args))
+        return llama_record(await run(*args, fields=fields))
 
     def llama_record(r: GenRequest) -> dict:
+        probs = {}
+        if r.logprobs is not None:
+            probs = {"completion_probabilities": [
+                {"id": e["id"], "token": e["token"], "bytes": utf8(e["token"]), "logprob": e["logprob"],
+                 "top_logprobs": [{"id": a, "token": t, "bytes": utf8(t), "logprob": b} for a, t, b in e["top"]]}
+                for e in token_entries(r)]}
+        return {**llama_record_base(r), **probs}
+
+    def llama_record_base(r: GenRequest) -> dict:
         return {"content": r.text, "model": model_name, "stop": True, "tokens_predicted": len(r.tokens),
                "tokens_evaluated": len(r.prompt_ids), "stopped_eos": r.finish == "stop" and not r.stopping_word,
                "stopped_word": bool(r.stopping_word), "stopped_limit": r.finish == "length",
@@ -426,7 +573,20 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
         return (o.get("num_predict", default_n_predict), o.get("temperature", 0.8), o.get("top_k", 40),
                 o.get("top_p", 0.9), o.get("min_p", 0.0), o.get("seed"), o.get("stop"))
 
+    def ollama_fields(body) -> dict:
+        # an absent repeat_penalty stays neutral here (Ollama's own default is 1.1): a new default
+        # would change every existing response
+        lp = body.get("logprobs")
+        top = number("top_logprobs", body.get("top_logprobs"), 0)
+        return logit_fields(dict(body.get("options") or {}), bias_pairs=True,
+                            n_probs=max(0, min(int(top), 20)) if lp else -1, stream=bool(body.get("stream", True)))
+
     def ollama_record(r: GenRequest, extra: dict) -> dict:
+        if r.logprobs is not None:
+            extra = {**extra, "logprobs": [
+                {"token": e["token"], "logprob": e["logprob"], "bytes": utf8(e["token"]),
+                 "top_logprobs": [{"token": t, "logprob": b, "bytes": utf8(t)} for _, t, b in e["top"]]}
+                for e in token_entries(r)]}
         return {"model": model_name, "created_at": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()), **extra,
                 "done": True, "done_reason": r.finish, "total_duration": int(1e9 * (r.prompt_s + r.gen_s)),
                 "load_duration": 0, "prompt_eval_count": len(r.prompt_ids),
@@ -443,29 +603,31 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
             prompt = chat_prompt([{"role": "system", "content": body["system"]}, {"role": "user", "content": prompt}],
                                  family)
         n, temp, k, p, mp, seed, stop = ollama_opts(body)
+        fields = ollama_fields(body)
         if body.get("stream", True):                 # Ollama streams unless told not to
-            return streamed(prepare(prompt, n, temp, k, p, mp, seed, stop),
+            return streamed(with_fields(prepare(prompt, n, temp, k, p, mp, seed, stop), fields),
                             lambda d: json.dumps({"model": model_name, "created_at": now_iso(), "response": d,
                                                   "done": False}) + "\n",
                             lambda r: json.dumps(ollama_record(r, {"response": "", "context": []}) if r else
                                                  {"error": "generation failed"}) + "\n",
                             "application/x-ndjson")
-        r = await run(prompt, n, temp, k, p, mp, seed, stop)
+        r = await run(prompt, n, temp, k, p, mp, seed, stop, fields=fields)
         return ollama_record(r, {"response": r.text, "context": []})
 
     @app.post("/api/chat")
     async def ollama_chat(body: dict = Body(...)):
         n, temp, k, p, mp, seed, stop = ollama_opts(body)
         prompt = chat_prompt(body.get("messages") or [], family)
+        fields = ollama_fields(body)
         if body.get("stream", True):
-            return streamed(prepare(prompt, n, temp, k, p, mp, seed, stop),
+            return streamed(with_fields(prepare(prompt, n, temp, k, p, mp, seed, stop), fields),
                             lambda d: json.dumps({"model": model_name, "created_at": now_iso(),
                                                   "message": {"role": "assistant", "content": d},
                                                   "done": False}) + "\n",
                             lambda r: json.dumps(ollama_record(r, {"message": {"role": "assistant", "content": ""}})
                                                  if r else {"error": "generation failed"}) + "\n",
                             "application/x-ndjson")
-        r = await run(prompt, n, temp, k, p, mp, seed, stop)
+        r = await run(prompt, n, temp, k, p, mp, seed, stop, fields=fields)
         return ollama_record(r, {"message": {"role": "assistant", "content": r.text}})
 
     @app.get("/api/tags")
@@ -496,17 +658,31 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
             prompt = prompt[0]
         args = (prompt, body.get("max_tokens", 16), body.get("temperature", 1.0), 0, body.get("top_p", 1.0), 0.0,
                 body.get("seed"), body.get("stop"))
+        n_lp = body.get("logprobs")
+        if n_lp is not None:
+            n_lp = number("logprobs", n_lp, 0)
+            if n_lp != int(n_lp) or not 0 <= n_lp <= 5:
+                bad("logprobs", "must be an integer from 0 to 5")
+        # OpenAI penalises the generated text only, all of it
+        fields = logit_fields(body, bias_pairs=False, last_n=-1, penalize_prompt=False, repeat=False,
+                              n_probs=-1 if n_lp is None else int(n_lp), stream=bool(body.get("stream")))
         cid, created = f"cmpl-{uuid.uuid4().hex[:24]}", int(time.time())
         head = {"id": cid, "object": "text_completion", "created": created, "model": model_name}
         if body.get("stream"):
-            return streamed(prepare(*args),
+            return streamed(with_fields(prepare(*args), fields),
                             lambda d: sse({**head, "choices": [{"text": d, "index": 0, "logprobs": None,
                                                                 "finish_reason": None}]}),
                             lambda r: sse({**head, "choices": [{"text": "", "index": 0, "logprobs": None,
                                                                 "finish_reason": r.finish if r else "error"}]}),
                             "text/event-stream", tail="data: [DONE]\n\n")
-        r = await run(*args)
-        choice = {"text": r.text, "index": 0, "logprobs": None, "finish_reason": r.finish}
+        r = await run(*args, fields=fields)
+        lps = None
+        if r.logprobs is not None:
+            ents = token_entries(r)
+            lps = {"tokens": [e["token"] for e in ents], "token_logprobs": [e["logprob"] for e in ents],
+                   "top_logprobs": [{t: b for _, t, b in reversed(e["top"])} for e in ents],
+                   "text_offset": [e["offset"] for e in ents]}
+        choice = {"text": r.text, "index": 0, "logprobs": lps, "finish_reason": r.finish}
         return {"id": cid, "object": "text_completion", "created": created, "model": model_name,
                 "choices": [choice], "usage": oai_usage(r)}
 
@@ -519,6 +695,18 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
             raise HTTPException(400, "messages must be a non-empty list")
         args = (chat_prompt(msgs, family), body.get("max_tokens", body.get("max_completion_tokens")),
                 body.get("temperature", 1.0), 0, body.get("top_p", 1.0), 0.0, body.get("seed"), body.get("stop"))
+        want_lp = body.get("logprobs")
+        if want_lp is not None and not isinstance(want_lp, bool):
+            bad("logprobs", "must be true or false")
+        top_lp = body.get("top_logprobs")
+        if top_lp is not None:
+            top_lp = number("top_logprobs", top_lp, 0)
+            if top_lp != int(top_lp) or not 0 <= top_lp <= 20:
+                bad("top_logprobs", "must be an integer from 0 to 20")
+            if not want_lp:
+                bad("top_logprobs", "needs logprobs: true")
+        fields = logit_fields(body, bias_pairs=False, last_n=-1, penalize_prompt=False, repeat=False,
+                              n_probs=int(top_lp or 0) if want_lp else -1, stream=bool(body.get("stream")))
         cid, created = f"chatcmpl-{uuid.uuid4().hex[:24]}", int(time.time())
         head = {"id": cid, "object": "chat.completion.chunk", "created": created, "model": model_name}
         if body.get("stream"):
@@ -528,14 +716,19 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
                 dd = {"content": d} if first["sent"] else {"role": "assistant", "content": d}
                 first["sent"] = True
                 return sse({**head, "choices": [{"index": 0, "delta": dd, "finish_reason": None}]})
-            return streamed(prepare(*args), delta,
+            return streamed(with_fields(prepare(*args), fields), delta,
                             lambda r: sse({**head, "choices": [{"index": 0, "delta": {},
                                                                 "finish_reason": r.finish if r else "error"}]}),
                             "text/event-stream", tail="data: [DONE]\n\n")
-        r = await run(*args)
+        r = await run(*args, fields=fields)
+        choice = {"index": 0, "message": {"role": "assistant", "content": r.text}, "finish_reason": r.finish}
+        if r.logprobs is not None:
+            choice["logprobs"] = {"content": [
+                {"token": e["token"], "logprob": e["logprob"], "bytes": utf8(e["token"]),
+                 "top_logprobs": [{"token": t, "logprob": b, "bytes": utf8(t)} for _, t, b in e["top"]]}
+                for e in token_entries(r)]}
         return {"id": cid, "object": "chat.completion", "created": created, "model": model_name,
-                "choices": [{"index": 0, "message": {"role": "assistant", "content": r.text},
-                             "finish_reason": r.finish}], "usage": oai_usage(r)}
+                "choices": [choice], "usage": oai_usage(r)}
 
     @app.get("/v1/models")
     def oai_models():
