@@ -52,6 +52,7 @@ _KERNEL_SIGS = {
     "cfc_embedding": [P, P, P, I, I, P],
     "cfc_sample": [P, I, I, F, c_uint32, P, P, P],
     "cfc_sample_truncated": [P, I, I, F, I, F, F, c_uint32, P, P, P],
+    "cfc_sample_rows": [P, I, I, P, P, P, P, P, P, P, P],
     "cfc_decode_advance": [P, P, I, P, P, P, P, P, P, I, P, P, I, I] + [P] * 6 + [I] * 4 + [P] * 4,
     "cfc_logit_processors": [P, I, I, P, I, P, P, P, P, P, I] + [P] * 8,
     "cfc_token_logprobs": [P, P, I, I, I, P, P, P, I, P, P, P, P],

@@ -1480,6 +1480,88 @@ def sample(logits, out_ids, temperature=0.0, seed=0, step=None):
     return out_ids
 
 
+class SamplerRows:
+    """Per-row sampler settings of :func:`sample_rows` in persistent tensors, one entry per slot: a
+    captured decode graph holds their pointers, the host rewrites a slot's entries when a request
+    takes it.  ``pos[row]`` counts the tokens the row's request has sampled; the kernel advances
+    it.  A free row is greedy with seed 0, so the idle rows of a width bucket do defined work."""
+
+    _FIELDS = ("temperature", "top_k", "top_p", "min_p", "seed", "pos")
+
+    def __init__(self, B: int, device):
+        self.B = int(B)
+        i32 = dict(dtype=torch.int32, device=device)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.temperature = torch.zeros(B, **f32)
+        self.top_k = torch.zeros(B, **i32)
+        self.top_p = torch.ones(B, **f32)
+        self.min_p = torch.zeros(B, **f32)
+        self.seed = torch.zeros(B, **i32)      # the uint32 seed's bit pattern
+        self.pos = torch.zeros(B, **i32)
+
+    @staticmethod
+    def check(sp: "SamplingParams") -> None:
+        if sp.temperature > 0 and not sp.top_p > 0:
+            raise ValueError("top_p must be positive")
+        if math.isnan(sp.temperature) or math.isnan(sp.top_p) or math.isnan(sp.min_p):
+            raise ValueError("sampler values must be numbers")
+
+    def set_rows(self, rows, params, seeds, pos: int = 0) -> None:
+        """Install ``params[i]`` (SamplingParams) and ``seeds[i]`` for row ``rows[i]`` and put the
+        rows' stream at ``pos``."""
+        rows = list(rows)
+        if not rows:
+            return
+        flt = torch.zeros(len(rows), 3, dtype=torch.float32)     # temperature, top_p, min_p
+        ints = torch.zeros(len(rows), 3, dtype=torch.int32)      # top_k, seed, pos
+        for i, (sp, seed) in enumerate(zip(params, seeds)):
+            sp = SamplingParams.of(sp)
+            self.check(sp)
+            s = int(seed) & 0xFFFFFFFF
+            flt[i] = torch.tensor([sp.temperature, sp.top_p, sp.min_p], dtype=torch.float32)
+            ints[i] = torch.tensor([int(sp.top_k), s - (1 << 32) if s >= 1 << 31 else s, int(pos)], dtype=torch.int32)
+        dev = self.pos.device
+        idx = torch.tensor(rows, dtype=torch.long, device=dev)
+        flt, ints = flt.to(dev), ints.to(dev)
+        for j, dst in enumerate((self.temperature, self.top_p, self.min_p)):
+            dst.index_copy_(0, idx, flt[:, j].contiguous())
+        for j, dst in enumerate((self.top_k, self.seed, self.pos)):
+            dst.index_copy_(0, idx, ints[:, j].contiguous())
+
+    def set(self, slot: int, sp: "SamplingParams", seed: int = 0) -> None:
+        self.set_rows([slot], [sp], [seed])
+
+    def reset(self, slot: int) -> None:
+        """Back to greedy / seed 0 / pos 0."""
+        self.set_rows([slot], [SamplingParams()], [0])
+
+
+def sample_rows(logits, out_ids, rows: SamplerRows, width: int | None = None):
+    """One token per row of ``logits`` [W, V] into ``out_ids`` [W] (int32), row b by the settings in
+    entry b of ``rows`` (``width`` = W, the first W entries): greedy, Gumbel-max over the whole row
+    or the truncated chain, what :func:`sample` gives for that row alone with the row's seed and
+    ``step = pos[b]``; ``pos[:W]`` advances by one.  Graph-capturable."""
+    W, V = logits.shape
+    width = W if width is None else int(width)
+    if width != W or W > rows.B or out_ids.shape[0] < W:
+        raise ValueError(f"sample_rows: {W} logit rows, width {width}, {rows.B} sampler rows")
+    _req(out_ids, torch.int32, "out_ids")
+    for f, dt in (("temperature", torch.float32), ("top_k", torch.int32), ("top_p", torch.float32),
+                  ("min_p", torch.float32), ("seed", torch.int32), ("pos", torch.int32)):
+        _req(getattr(rows, f), dt, f)
+    if not logits.is_cuda:
+        out_ids[:W].copy_(ref.sample_rows(logits, rows.temperature[:W].tolist(), rows.top_k[:W].tolist(),
+                                          rows.top_p[:W].tolist(), rows.min_p[:W].tolist(), rows.seed[:W].tolist(),
+                                          rows.pos[:W].tolist()))
+        rows.pos[:W] += 1
+        return out_ids
+    _req(logits, torch.bfloat16, "logits")
+    check(kernels().cfc_sample_rows(logits.data_ptr(), W, V, rows.temperature.data_ptr(), rows.top_k.data_ptr(),
+                                    rows.top_p.data_ptr(), rows.min_p.data_ptr(), rows.seed.data_ptr(),
+                                    rows.pos.data_ptr(), out_ids.data_ptr(), _stream(logits)), "cfc_sample_rows")
+    return out_ids
+
+
 PENALTY_WINDOW_MAX = 1024   # history tokens kept per row for the penalties (logits.hip: PEN_WINDOW_CAP)
 LOGIT_BIAS_MAX = 512        # logit_bias entries per row (logits.hip: BIAS_CAP)
 TOP_LOGPROBS_MAX = 20       # top log-probabilities per record (logits.hip: TOPLP_CAP)

@@ -273,6 +273,23 @@ def sample_truncated(logits, temperature, top_k, top_p, min_p, generator=None, c
     return torch.tensor(out, dtype=torch.int32)
 
 
+def sample_rows(logits, temperature, top_k, top_p, min_p, seed, pos):
+    """Every row with its own settings (sequences of length B): ``temperature <= 0`` rows take
+    :func:`sample_greedy`, the others :func:`sample_truncated` with a generator seeded from the
+    row's (seed, pos) alone -- so, as on the GPU, a row's draw does not depend on which row it is
+    or on what the other rows ask for.  ``pos`` is not advanced here."""
+    out = sample_greedy(logits).clone()
+    for b in range(logits.shape[0]):
+        if float(temperature[b]) <= 0:
+            continue
+        # (the CPU generator keeps 32 bits of its seed: fold both words into them)
+        h = ((int(seed[b]) & 0xFFFFFFFF) * 0x9E3779B97F4A7C15 + (int(pos[b]) & 0xFFFFFFFF) * 0xBF58476D1CE4E5B9) % (1 << 64)
+        g = torch.Generator().manual_seed((h ^ (h >> 32)) & 0xFFFFFFFF)
+        out[b] = sample_truncated(logits[b:b + 1], float(temperature[b]), int(top_k[b]), float(top_p[b]),
+                                  float(min_p[b]), g)[0]
+    return out
+
+
 def penalty_window(history, last_n: int, window_max: int) -> list[int]:
     """The tokens a row's penalties see: the last ``last_n`` of its history (prompt tail ++
     generated); 0 = none, negative or above ``window_max`` = as much as is kept."""

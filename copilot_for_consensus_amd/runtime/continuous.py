@@ -55,6 +55,8 @@ class Request:
     logit: object = None                 # ops.kernels.LogitParams (engines built with processors)
     n_logprobs: int = -1                 # top log-probabilities wanted per token (-1: none)
     logprobs: list | None = None         # one (chosen logprob, [(id, logprob), ...]) per token
+    sampling: object = None              # ops.kernels.SamplingParams and seed of the request's own
+    seed: int = 0                        # (engines built with per_request_sampling)
 
     @property
     def latency_s(self) -> float | None:
@@ -66,11 +68,15 @@ class ContinuousEngine:
                  steps_per_sync: int = 16, stop_ids: tuple[int, ...] = (), temperature: float = 0.0, seed: int = 0,
                  max_admit_tokens: int | None = None, min_admit: int = 1, max_wait_s: float = 0.5,
                  stop_strings=None, bulk_admit_frac: float = 0.5, sync=None, processors: bool = False,
-                 logprobs: int = -1):
+                 logprobs: int = -1, per_request_sampling: bool = False):
         """``processors`` / ``logprobs``: whether the captured step carries the logit-processor
         kernel / records each token's log-probability and the ``logprobs`` most probable tokens'
         (-1: no records).  They are properties of the engine and its graph; the penalties, biases
-        and the number of top entries a request reads back are per request (:meth:`submit`)."""
+        and the number of top entries a request reads back are per request (:meth:`submit`).
+        ``per_request_sampling``: the captured step samples every slot by its own temperature,
+        top-k, top-p, min-p and seed (ops.kernels.sample_rows over per-slot arrays) instead of by
+        the engine's one ``temperature`` / ``seed``; a request's draws then depend on its seed, its
+        own token index and the logits only, not on its slot or on the engine's age."""
         self.engine = engine
         # TP leader: called with each step's decision before any device work (see the module doc)
         self.sync = sync
@@ -87,6 +93,10 @@ class ContinuousEngine:
             self.sampling = dataclasses.replace(self.sampling, processors=bool(processors) or self.sampling.processors,
                                                 logprobs=max(int(logprobs), self.sampling.logprobs))
         self.seed = int(seed)
+        self.per_request_sampling = bool(per_request_sampling)
+        if self.per_request_sampling and getattr(engine.model.w, "tp_size", 1) > 1:
+            # the followers replay the leader's admissions, which do not carry the sampler values
+            raise ValueError("per_request_sampling is not supported with tensor parallel (TP > 1)")
         self.max_admit_tokens = max_admit_tokens or engine.max_prefill_tokens * 4
         # admission batching: prefill waits for `min_admit` queued threads (or the oldest waiting
         # `max_wait_s`, or an idle engine) -- fewer, larger prefills interrupt the decode less
@@ -113,6 +123,8 @@ class ContinuousEngine:
         self.done = torch.ones(B, **i32)
         self.next_ids = torch.zeros(B, **i32)
         self.step_t = torch.zeros(1, **i32)     # sampler RNG salt
+        # per-slot sampler settings and stream positions; free slots are greedy / seed 0
+        self.sampler_rows = K.SamplerRows(B, dev) if self.per_request_sampling else None
         # leading KV blocks every occupied slot shares (prefix cache): read through the caches
         self.shared = torch.zeros(1, **i32)
         self._slot_shared = [0] * B
@@ -148,11 +160,14 @@ class ContinuousEngine:
         self.admit_log: list[tuple] = []     # (admit time, requests, first arrival, last arrival), epoch s
 
     # ------------------------------------------------------------------ API
-    def submit(self, prompt: list[int], max_new: int, logprobs: int | None = None, **logit_kw) -> Request:
+    def submit(self, prompt: list[int], max_new: int, logprobs: int | None = None, sampling=None, seed: int = 0,
+               **logit_kw) -> Request:
         """``logit_kw``: repeat_penalty, repeat_last_n, presence_penalty, frequency_penalty,
         logit_bias, penalize_prompt (ops.kernels.LogitParams) -- this request's own, beside other
         requests' in the same captured step; ``logprobs`` = N: its result carries each token's
-        log-probability and the N most probable tokens'.  Both need an engine built with them."""
+        log-probability and the N most probable tokens'.  Both need an engine built with them.
+        ``sampling`` (SamplingParams or a temperature) and ``seed``: this request's sampler, on an
+        engine built with ``per_request_sampling`` (default there: greedy)."""
         if not prompt:
             raise ValueError("empty prompt")
         if len(prompt) > self.max_prompt or max_new > self.cap or max_new < 1:
@@ -163,7 +178,14 @@ class ContinuousEngine:
         n_lp = -1 if logprobs is None else int(logprobs)
         if n_lp > self.sampling.logprobs:
             raise ValueError(f"this engine records at most {self.sampling.logprobs} top logprobs")
-        r = Request(self._rid, list(prompt), int(max_new), time.perf_counter(), logit=lp, n_logprobs=n_lp)
+        if (sampling is not None or seed) and not self.per_request_sampling:
+            raise ValueError("this engine was built without per_request_sampling")
+        sp = None
+        if self.per_request_sampling:
+            sp = K.SamplingParams.of(0.0 if sampling is None else sampling)
+            K.SamplerRows.check(sp)
+        r = Request(self._rid, list(prompt), int(max_new), time.perf_counter(), logit=lp, n_logprobs=n_lp,
+                    sampling=sp, seed=int(seed))
         self._rid += 1
         self.queue.append(r)
         return r
@@ -328,8 +350,12 @@ class ContinuousEngine:
         t = time.perf_counter()
         try:
             ls, rec0 = self._logit_state(), {}
-            if ls is not None:
-                lps = [r.logit or K.LogitParams() for r in take]
+            lps = [r.logit or K.LogitParams() for r in take] if ls is not None else None
+            if self.per_request_sampling:
+                sampler = [(r.sampling or K.SamplingParams(), r.seed) for r in take]
+                first = self.engine._prefill([r.prompt for r in take], tables, self.sampling, self.seed, start,
+                                             lps, rec0, sampler)
+            elif ls is not None:
                 first = self.engine._prefill([r.prompt for r in take], tables, self.sampling, self.seed, start,
                                              lps, rec0)
             else:
@@ -376,6 +402,9 @@ class ContinuousEngine:
                 ls.lp[slots[i], 0] = lp0[0]
                 ls.top_ids[slots[i], 0] = ids0[0]
                 ls.top_lp[slots[i], 0] = top0[0]
+        if self.sampler_rows is not None:
+            # the prefill drew token 0 of each request's stream: the decode steps go on from 1
+            self.sampler_rows.set_rows(slots, [p for p, _ in sampler], [sd for _, sd in sampler], pos=1)
         self.tokens.index_copy_(0, idx, torch.nn.functional.pad(rows_t[:, :1], (0, self.cap - 1)))
         self.stats["admitted"] += len(take)
         # admission timeline (wall clock): when, how many, first / last arrival of the admitted requests
@@ -393,8 +422,13 @@ class ContinuousEngine:
         hidden = self.model.forward_decode(self.ids[:W], self.positions[:W], self.slots[:W], self.ctx_lens[:W],
                                            self.block_tables[:W], self.kv, attn_workspace=self.workspace,
                                            part_blocks=self._pb[W], shared_blocks=self.shared)
+        ctx = None
         if self.sampling.logit_state:
             ctx = K.LogitCtx(self._logit_state().view(W), tokens=self.tokens[:W], gen=self.gen[:W], done=self.done[:W])
+        if self.sampler_rows is not None:
+            self.engine._next_tokens(hidden, self.next_ids[:W], self.sampling, self.seed, self.step_t, ctx,
+                                     self.sampler_rows)
+        elif ctx is not None:
             self.engine._next_tokens(hidden, self.next_ids[:W], self.sampling, self.seed, self.step_t, ctx)
         else:
             self.engine._next_tokens(hidden, self.next_ids[:W], self.sampling, self.seed, self.step_t)
@@ -405,6 +439,8 @@ class ContinuousEngine:
 
     def _state(self):
         extra = [self.stop_state.win, self.stop_state.wlen, self.stop_state.keep] if self.stop_state else []
+        if self.sampler_rows is not None:
+            extra = extra + [self.sampler_rows.pos]
         return [self.ids, self.positions, self.ctx_lens, self.slots, self.tokens, self.gen, self.done,
                 self.next_ids, self.step_t] + extra
 
@@ -470,6 +506,8 @@ class ContinuousEngine:
         self.slots.index_fill_(0, idx, self.scratch * KV_BLOCK)
         self.positions.index_fill_(0, idx, 0)
         self.ctx_lens.index_fill_(0, idx, 1)
+        if self.sampler_rows is not None:
+            self.sampler_rows.set_rows(fin, [K.SamplingParams()] * len(fin), [0] * len(fin))
         self.stats["finished"] += len(out)
         return out
 

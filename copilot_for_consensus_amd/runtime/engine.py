@@ -179,12 +179,15 @@ class LLMEngine:
             print(f"[ar-debug] rank {ar.rank} {tag}: errors={ar.errors()} epochs[0:4]={ep[:4]} "
                   f"epochs[32]={ep[32]} key={ep[-1]} distinct={sorted(set(ep))[:6]}", flush=True)
 
-    def _prefill(self, prompts, tables, temperature, seed, start=None, logit=None, records=None):
+    def _prefill(self, prompts, tables, temperature, seed, start=None, logit=None, records=None, sampler=None):
         """Chunked packed prefill; returns first sampled token per prompt.  ``start[s]`` tokens of
         prompt s are already in the cache (shared prefix blocks).  ``logit[s]`` (LogitParams, when
         the sampling has processors / logprobs on): the first token gets the same treatment as the
         decode steps' -- nothing generated yet, so its window is the prompt tail; its
-        log-probability record lands in ``records[s]`` = (lp [1], ids [1, N], top [1, N])."""
+        log-probability record lands in ``records[s]`` = (lp [1], ids [1, N], top [1, N]).
+        ``sampler[s]`` = (SamplingParams, seed): prompt s's own sampler settings; its first token is
+        then drawn by :func:`ops.kernels.sample_rows` at position 0 of its stream (``temperature``
+        and ``seed`` only say whether the processors / records run)."""
         n = len(prompts)
         sp = K.SamplingParams.of(temperature)
         first_dev = torch.zeros(n, dtype=torch.int32, device=self.device)
@@ -219,7 +222,12 @@ class LLMEngine:
                                     [prompts[s] for s in finishing])
                         ctx = K.LogitCtx(ls)
                     step0 = torch.zeros(1, dtype=torch.int32, device=self.device)
-                    if ctx is None:
+                    if sampler is not None:
+                        rows = K.SamplerRows(len(finishing), self.device)
+                        rows.set_rows(range(len(finishing)), [sampler[s][0] for s in finishing],
+                                      [sampler[s][1] for s in finishing])
+                        self._next_tokens(hidden, out, temperature, seed, step0, ctx, rows)
+                    elif ctx is None:
                         self._next_tokens(hidden, out, temperature, seed, step0)
                     else:
                         self._next_tokens(hidden, out, temperature, seed, step0, ctx)
@@ -306,17 +314,25 @@ class LLMEngine:
             return self._tp_greedy(temperature) and self.model.graph_collectives_ok(B)
         return True
 
-    def _next_tokens(self, hidden, out, temperature, seed, step, logit=None):
+    def _next_tokens(self, hidden, out, temperature, seed, step, logit=None, rows=None):
         """Sample the next token of every row; TP greedy reduces (max, argmax) keys instead of
         all-gathering the logits (DecoderModel.greedy_ids).  ``logit`` (ops.kernels.LogitCtx), with
         ``processors`` / ``logprobs`` in the sampling parameters: raw logits -> processors (on a
         copy when the raw ones are still needed) -> sample -> log-probability record of the raw
-        logits.  With neither on, the launches are the ones above and nothing else."""
-        if self._tp_greedy(temperature):
-            return self.model.greedy_ids(hidden, out)
+        logits.  With neither on, the launches are the ones above and nothing else.  ``rows``
+        (ops.kernels.SamplerRows): every row is sampled by its own entry (sample_rows over the first
+        ``len(out)`` entries) instead of by ``temperature`` / ``seed`` / ``step``."""
         sp = K.SamplingParams.of(temperature)
+        if rows is not None:
+            if getattr(self.model.w, "tp_size", 1) > 1:
+                raise ValueError("per-row sampler settings are not supported with tensor parallel (TP > 1)")
+            draw = lambda x: K.sample_rows(x, out, rows, out.shape[0])  # noqa: E731
+        else:
+            if self._tp_greedy(temperature):
+                return self.model.greedy_ids(hidden, out)
+            draw = lambda x: K.sample(x, out, sp, seed, step)  # noqa: E731
         if not sp.logit_state:
-            return K.sample(self.model.logits(hidden), out, temperature, seed, step)
+            return draw(self.model.logits(hidden))
         if logit is None:
             raise ValueError("processors / logprobs need a logit state")
         raw = self.model.logits(hidden)
@@ -326,7 +342,7 @@ class LLMEngine:
                 x = logit.state.work(raw)
                 x.copy_(raw)
             K.logit_processors(x, logit)
-        K.sample(x, out, sp, seed, step)
+        draw(x)
         if sp.logprobs >= 0:
             K.token_logprobs(raw, out, logit, sp.logprobs)
         return out

@@ -14,7 +14,8 @@ Concurrent requests share the GPU through continuous batching: each distinct sam
 configuration gets a slot-based engine (runtime/continuous.py) whose hipGraph-captured decode step
 runs over every in-flight request, and new requests are admitted between bursts; per-request token
 limits, EOS and stop strings are applied per row.  Requests beyond the slot engine's caps fall back
-to grouped batched ``LLMEngine.generate`` calls.
+to grouped batched ``LLMEngine.generate`` calls.  With ``per_request_sampling`` the sampler values
+and the seed are per-slot too, and requests of any sampling configuration share one engine.
 
 Routes:
   llama.cpp  POST /completion, POST /tokenize, POST /detokenize, GET /health, GET /props
@@ -105,17 +106,29 @@ class GenRequest:
             key += ((self.processors, self.n_probs >= 0),)
         return key
 
+    def engine_key(self):
+        """What requests must share to share a slot engine whose step samples every slot by its own
+        settings (``per_request_sampling``): the stop ids and which logit kernels the step carries."""
+        key = (self.ignore_eos,)
+        if self.processors or self.n_probs >= 0:
+            key += ((self.processors, self.n_probs >= 0),)
+        return key
+
 
 class BatchScheduler:
     """Runs requests on the engine: continuous batching (runtime/continuous.py: one hipGraph-captured
     decode step over a fixed set of slots, requests admitted between bursts) for each distinct
     sampling configuration, up to ``max_engines`` of them; requests beyond a continuous engine's
     prompt / token caps, or past that many configurations, run as grouped batched ``generate``
-    calls (micro-batching)."""
+    calls (micro-batching).  ``per_request_sampling``: temperature, top-k, top-p, min-p and seed are
+    per-slot values of one engine's step, so requests are grouped by :meth:`GenRequest.engine_key`
+    alone and only those over the caps take the ``generate`` path."""
 
     def __init__(self, engine, tokenizer, max_batch: int = 64, batch_wait_ms: float = 5.0, continuous: bool = True,
-                 max_engines: int = 4, max_prompt: int = 4096, max_new_cap: int = 512, steps_per_sync: int = 8):
+                 max_engines: int = 4, max_prompt: int = 4096, max_new_cap: int = 512, steps_per_sync: int = 8,
+                 per_request_sampling: bool = False):
         self.engine, self.tok = engine, tokenizer
+        self.per_request_sampling = bool(per_request_sampling)
         self.max_batch, self.wait_s = int(max_batch), batch_wait_ms / 1000.0
         self.continuous, self.max_engines = continuous, int(max_engines)
         self.max_prompt, self.cap, self.steps_per_sync = int(max_prompt), int(max_new_cap), int(steps_per_sync)
@@ -156,22 +169,27 @@ class BatchScheduler:
         self._t.join(5)
 
     # ------------------------------------------------------------------ scheduling
+    def _key(self, r: GenRequest):
+        return r.engine_key() if self.per_request_sampling else r.key()
+
     def _continuous_for(self, r: GenRequest):
         if not self.continuous or len(r.prompt_ids) > self.max_prompt or r.max_new > self.cap:
             return None
-        key = r.key()
+        key = self._key(r)
         ce = self.engines.get(key)
         if ce is None:
-            if len(self.engines) >= self.max_engines:
+            # (with per-request sampling there are at most four engine keys)
+            if len(self.engines) >= self.max_engines and not self.per_request_sampling:
                 return None
             from ..ops import kernels as K
             from ..runtime.continuous import ContinuousEngine
             stops = () if r.ignore_eos else (self.engine.cfg.eos_id,)
             ce = ContinuousEngine(self.engine, max_slots=self.max_batch, max_new_cap=self.cap,
                                   max_prompt=self.max_prompt, steps_per_sync=self.steps_per_sync, stop_ids=stops,
-                                  seed=r.seed, max_wait_s=self.wait_s)
-            ce.sampling = K.SamplingParams(r.temperature, r.top_k, r.top_p, r.min_p) if r.temperature > 0 \
-                else K.SamplingParams.of(0.0)
+                                  seed=0 if self.per_request_sampling else r.seed, max_wait_s=self.wait_s,
+                                  per_request_sampling=self.per_request_sampling)
+            ce.sampling = K.SamplingParams(r.temperature, r.top_k, r.top_p, r.min_p) \
+                if r.temperature > 0 and not self.per_request_sampling else K.SamplingParams.of(0.0)
             if r.processors or r.n_probs >= 0:
                 ce.sampling = dataclasses.replace(ce.sampling, processors=r.processors,
                                                   logprobs=K.TOP_LOGPROBS_MAX if r.n_probs >= 0 else -1)
@@ -211,13 +229,22 @@ class BatchScheduler:
                 if ce is None:
                     legacy.setdefault(r.key(), []).append(r)
                 else:
+                    kw = {}
+                    if self.per_request_sampling:
+                        from ..ops.kernels import SamplingParams
+                        kw = dict(sampling=SamplingParams(r.temperature, r.top_k, r.top_p, r.min_p), seed=r.seed)
                     if r.processors or r.n_probs >= 0:
-                        cr = ce.submit(r.prompt_ids, r.max_new, logprobs=r.n_probs if r.n_probs >= 0 else None,
-                                       **r.logit_kw())
-                    else:
-                        cr = ce.submit(r.prompt_ids, r.max_new)
-                    r.handle = (r.key(), cr)
-                    self._inflight[r.key()][cr.rid] = r
+                        kw.update(r.logit_kw(), logprobs=r.n_probs if r.n_probs >= 0 else None)
+                    try:
+                        cr = ce.submit(r.prompt_ids, r.max_new, **kw)
+                    except ValueError as e:      # this request's values; the engine and the others go on
+                        if not self.per_request_sampling:
+                            raise
+                        r.error = f"ValueError: {e}"
+                        r.complete()
+                        continue
+                    r.handle = (self._key(r), cr)
+                    self._inflight[self._key(r)][cr.rid] = r
             for g in legacy.values():
                 # generate() applies one set of penalties to its whole batch: such requests run alone
                 plain = [r for r in g if not (r.processors or r.n_probs >= 0)]
@@ -347,10 +374,12 @@ def chat_prompt(messages: list[dict], family: str) -> str:
 
 def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, family: str = "mistral",
                    max_batch: int = 64, batch_wait_ms: float = 5.0, default_n_predict: int = 512,
-                   continuous: bool = True, max_prompt: int = 4096, max_new_cap: int = 512) -> FastAPI:
+                   continuous: bool = True, max_prompt: int = 4096, max_new_cap: int = 512,
+                   per_request_sampling: bool = False) -> FastAPI:
     sched = BatchScheduler(engine, tokenizer, max_batch=max_batch, batch_wait_ms=batch_wait_ms, continuous=continuous,
                            max_prompt=min(max_prompt, context_limit - 1),
-                           max_new_cap=max(1, min(max_new_cap, context_limit - 1)))
+                           max_new_cap=max(1, min(max_new_cap, context_limit - 1)),
+                           per_request_sampling=per_request_sampling)
     app = FastAPI(title=f"copilot-for-consensus HIP LLM server ({model_name})")
     app.state.scheduler = sched
     started = time.time()
@@ -745,11 +774,12 @@ def create_llm_app(engine, tokenizer, model_name: str, context_limit: int, famil
 
 def build_from_config(cfg: dict[str, Any], **server_kw):
     """(app, summarizer) from the ``llm_backend`` hip driver settings (LLM_MODEL_PRESET / LLM_GGUF_PATH /
-    LLM_CHECKPOINT_DIR / LLM_KV_CACHE_TOKENS / LLM_MAX_BATCH ...)."""
+    LLM_CHECKPOINT_DIR / LLM_KV_CACHE_TOKENS / LLM_MAX_BATCH / LLM_PER_REQUEST_SAMPLING ...)."""
     from ..summarization import HipLLMSummarizer
     s = HipLLMSummarizer(**{k: v for k, v in cfg.items() if v is not None})
     name = s.cfg.name
     family = "llama3" if "llama-3" in name or "llama3" in name or s.cfg.vocab_size > 100000 else "mistral"
     app = create_llm_app(s.engine, s.tokenizer, name, s.cfg.max_positions, family=family,
-                         max_batch=s.max_batch, default_n_predict=s.max_new_tokens, **server_kw)
+                         max_batch=s.max_batch, default_n_predict=s.max_new_tokens,
+                         **{"per_request_sampling": bool(cfg.get("per_request_sampling") or False), **server_kw})
     return app, s

@@ -260,15 +260,20 @@ __device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
 // lowest index) instead of an index that matched no comparison.
 __device__ __forceinline__ float logit_nan_as_ninf(float x) { return x != x ? -INFINITY : x; }
 
-// One workgroup per row. temperature <= 0 => greedy argmax (lowest index wins ties);
-// otherwise Gumbel-max sampling: argmax(logit/T + Gumbel(seed, step, row, idx)), which draws
-// exactly from softmax(logit/T).  `step` is read from device memory so graph replays advance it.
-__global__ void __launch_bounds__(1024) sample_kernel(const uint16_t* __restrict__ logits, int V, float temperature,
-                                                     uint32_t seed, const int32_t* __restrict__ step_ptr,
-                                                     int32_t* __restrict__ out_ids) {
-  const int row = blockIdx.x;
-  const uint16_t* lr = logits + (size_t)row * V;
-  const uint32_t step = step_ptr ? (uint32_t)*step_ptr : 0u;
+// The counter-based uniform behind every sampler draw: a function of (seed, step, rng row, token id).
+__device__ __forceinline__ float sample_uniform(uint32_t seed, uint32_t step, uint32_t rng_row, int idx) {
+  const uint32_t h = hash_u32(seed ^ hash_u32(step * 0x9E3779B9u ^ hash_u32(rng_row * 0x85EBCA6Bu ^ (uint32_t)idx)));
+  return ((h >> 8) + 0.5f) * (1.f / 16777216.f);
+}
+
+// One workgroup per row, any block size that is a multiple of 64 up to 1024 (the result is an
+// argmax under a total order, so it does not depend on the block size or on LOADS).
+// temperature <= 0 => greedy argmax (lowest index wins ties); otherwise Gumbel-max sampling:
+// argmax(logit/T + Gumbel(seed, step, rng_row, idx)), which draws exactly from softmax(logit/T).
+// LOADS independent 16-B loads per thread are in flight per trip over the row.
+template <int LOADS>
+__device__ __forceinline__ void sample_row(const uint16_t* __restrict__ lr, int V, float temperature, uint32_t seed,
+                                           uint32_t step, uint32_t rng_row, int32_t* __restrict__ out) {
   float best = -INFINITY;
   int best_i = 0x7fffffff;
   const int nvec = (V % 8 == 0) ? V / 8 : 0;  // 16-byte row alignment needed for vector loads
@@ -277,23 +282,21 @@ __global__ void __launch_bounds__(1024) sample_kernel(const uint16_t* __restrict
   auto score = [&](float x, int idx) -> float {
     x = logit_nan_as_ninf(x);
     if (!sample) return x;
-    const uint32_t h = hash_u32(seed ^ hash_u32(step * 0x9E3779B9u ^ hash_u32(row * 0x85EBCA6Bu ^ (uint32_t)idx)));
-    const float u = ((h >> 8) + 0.5f) * (1.f / 16777216.f);
-    return x * inv_t - __logf(-__logf(u));
+    return x * inv_t - __logf(-__logf(sample_uniform(seed, step, rng_row, idx)));
   };
-  // 1024 threads x 4 independent 16-B loads in flight: a 32k-vocab row is one memory round trip
-  // (the previous 256-thread loop was 16 dependent ones: 16 us per decode step at B = 1)
-  for (int c0 = threadIdx.x; c0 < nvec; c0 += 4 * blockDim.x) {
-    uint4 raw[4];
+  // 1024 threads x 4 (or 256 x 16) independent 16-B loads in flight: a 32k-vocab row is one memory
+  // round trip (the previous 256-thread loop was 16 dependent ones: 16 us per decode step at B = 1)
+  for (int c0 = threadIdx.x; c0 < nvec; c0 += LOADS * blockDim.x) {
+    uint4 raw[LOADS];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < LOADS; ++u) {
       const int c = c0 + u * blockDim.x;
       raw[u] = c < nvec ? reinterpret_cast<const uint4*>(lr)[c] : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < LOADS; ++u) {
       const int c = c0 + u * blockDim.x;
-      if (c >= nvec) break;
+      if (c >= nvec) continue;   // (c grows with u; no early exit, so raw[] stays in registers)
       float v[8];
       unpack8(raw[u], v);
 #pragma unroll
@@ -324,8 +327,17 @@ __global__ void __launch_bounds__(1024) sample_kernel(const uint16_t* __restrict
       if (sb[i] > best || (sb[i] == best && si[i] < best_i)) { best = sb[i]; best_i = si[i]; }
     // an all-NaN / all -inf row matches no comparison: emit token 0 instead of an index past the
     // vocabulary (the next step's embedding gather would read outside the table)
-    out_ids[row] = (unsigned)best_i < (unsigned)V ? best_i : 0;
+    *out = (unsigned)best_i < (unsigned)V ? best_i : 0;
   }
+}
+
+// `step` is read from device memory so graph replays advance it; the RNG row is the batch row.
+__global__ void __launch_bounds__(1024) sample_kernel(const uint16_t* __restrict__ logits, int V, float temperature,
+                                                     uint32_t seed, const int32_t* __restrict__ step_ptr,
+                                                     int32_t* __restrict__ out_ids) {
+  const int row = blockIdx.x;
+  const uint32_t step = step_ptr ? (uint32_t)*step_ptr : 0u;
+  sample_row<4>(logits + (size_t)row * V, V, temperature, seed, step, (uint32_t)row, out_ids + row);
 }
 
 // Truncated sampling with llama.cpp's default chain (its server's /completion, which the reference
@@ -343,13 +355,12 @@ __device__ __forceinline__ uint32_t order_key(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ void __launch_bounds__(256) sample_topk_kernel(const uint16_t* __restrict__ logits, int V, float temperature,
-                                                          int top_k, float top_p, float min_p, uint32_t seed,
-                                                          const int32_t* __restrict__ step_ptr,
-                                                          int32_t* __restrict__ out_ids) {
-  const int row = blockIdx.x, tid = threadIdx.x;
-  const uint16_t* lr = logits + (size_t)row * V;
-  const uint32_t step = step_ptr ? (uint32_t)*step_ptr : 0u;
+// The body: one row by one workgroup of exactly 256 threads (the histogram bins, the four waves'
+// quarters of the tie scan and the rank pass are laid out for it).
+__device__ __forceinline__ void sample_topk_row(const uint16_t* __restrict__ lr, int V, float temperature, int top_k,
+                                                float top_p, float min_p, uint32_t seed, uint32_t step,
+                                                uint32_t rng_row, int32_t* __restrict__ out) {
+  const int tid = threadIdx.x;
   const int K = max(1, min(top_k > 0 ? top_k : SK_CAP, min(V, SK_CAP)));
   __shared__ uint32_t hist[256];
   __shared__ uint32_t s_prefix, s_remaining;
@@ -457,11 +468,7 @@ __global__ void __launch_bounds__(256) sample_topk_kernel(const uint16_t* __rest
     int best_i = 0x7fffffff;
     for (int j = tid; j < s_keep; j += 64) {
       float x = sv[j];
-      if (temperature > 0.f) {
-        const uint32_t h = hash_u32(seed ^ hash_u32(step * 0x9E3779B9u ^ hash_u32(row * 0x85EBCA6Bu ^ (uint32_t)si[j])));
-        const float u = ((h >> 8) + 0.5f) * (1.f / 16777216.f);
-        x = x / temperature - __logf(-__logf(u));
-      }
+      if (temperature > 0.f) x = x / temperature - __logf(-__logf(sample_uniform(seed, step, rng_row, si[j])));
       if (x > best || (x == best && si[j] < best_i)) { best = x; best_i = si[j]; }
     }
 #pragma unroll
@@ -470,8 +477,55 @@ __global__ void __launch_bounds__(256) sample_topk_kernel(const uint16_t* __rest
       const int oi = __shfl_xor(best_i, o, 64);
       if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
     }
-    if (tid == 0) out_ids[row] = (unsigned)best_i < (unsigned)V ? best_i : 0;  // never outside the vocabulary
+    if (tid == 0) *out = (unsigned)best_i < (unsigned)V ? best_i : 0;  // never outside the vocabulary
   }
+}
+
+__global__ void __launch_bounds__(256) sample_topk_kernel(const uint16_t* __restrict__ logits, int V, float temperature,
+                                                          int top_k, float top_p, float min_p, uint32_t seed,
+                                                          const int32_t* __restrict__ step_ptr,
+                                                          int32_t* __restrict__ out_ids) {
+  const int row = blockIdx.x;
+  const uint32_t step = step_ptr ? (uint32_t)*step_ptr : 0u;
+  sample_topk_row(logits + (size_t)row * V, V, temperature, top_k, top_p, min_p, seed, step, (uint32_t)row,
+                  out_ids + row);
+}
+
+// Per-row sampler settings (struct of arrays, one entry per batch row; the continuous engine keeps
+// one entry per slot and rewrites a slot's when a request takes it).  pos[row] = tokens the row's
+// request has sampled so far: it takes the place of the engine step in the random stream, and the
+// batch-row term is fixed to 0, so a row draws from (seed[row], pos[row], token id) only -- the
+// result is the one sample_kernel / sample_topk_kernel give for that row alone (B = 1) with
+// seed = seed[row] and *step_ptr = pos[row].
+struct SampleRows {
+  const float* temperature;
+  const int32_t* top_k;
+  const float* top_p;
+  const float* min_p;
+  const uint32_t* seed;
+  int32_t* pos;
+};
+
+// One 256-thread workgroup per row: the block size the truncation body needs; the argmax body runs
+// at it with 16 loads in flight per thread (a 32k-vocab row is still one round trip).  The mode
+// depends on the row's values only, so the branch is uniform over the workgroup.  Thread 0
+// advances pos[row] after every thread has read it (both bodies pass a barrier first), so graph
+// replays move the stream on without the host.
+__global__ void __launch_bounds__(256) sample_rows_kernel(const uint16_t* __restrict__ logits, int V, SampleRows p,
+                                                          int32_t* __restrict__ out_ids) {
+  const int row = blockIdx.x;
+  const uint16_t* lr = logits + (size_t)row * V;
+  const float temperature = p.temperature[row];
+  const int top_k = p.top_k[row];
+  const float top_p = p.top_p[row], min_p = p.min_p[row];
+  const uint32_t seed = p.seed[row];
+  const int32_t pos = p.pos[row];
+  const bool truncated = temperature > 0.f && (top_k > 0 || top_p < 1.f || min_p > 0.f);
+  if (truncated)
+    sample_topk_row(lr, V, temperature, top_k, top_p, min_p, seed, (uint32_t)pos, 0u, out_ids + row);
+  else
+    sample_row<16>(lr, V, temperature, seed, (uint32_t)pos, 0u, out_ids + row);
+  if (threadIdx.x == 0) p.pos[row] = pos + 1;
 }
 
 // Advance the per-sequence decode state after sampling (one thread per sequence):
@@ -725,6 +779,18 @@ CFC_API int cfc_sample_truncated(const void* logits, int B, int V, float tempera
   if (V <= 0 || top_p <= 0.f) return -1;
   sample_topk_kernel<<<B, 256, 0, stream>>>((const uint16_t*)logits, V, temperature, top_k, top_p, min_p, seed,
                                             step_ptr, out_ids);
+  return CFC_CHECK_LAUNCH();
+}
+
+// Every row with its own temperature / top_k / top_p / min_p / seed and its own position in the
+// random stream (SampleRows); pos[row] is advanced by one.  A row's top_p <= 0 keeps its best token.
+CFC_API int cfc_sample_rows(const void* logits, int B, int V, const float* temperature, const int32_t* top_k,
+                            const float* top_p, const float* min_p, const uint32_t* seed, int32_t* pos,
+                            int32_t* out_ids, hipStream_t stream) {
+  if (B == 0) return 0;
+  if (B < 0 || V <= 0 || !logits || !temperature || !top_k || !top_p || !min_p || !seed || !pos || !out_ids) return -1;
+  const SampleRows p{temperature, top_k, top_p, min_p, seed, pos};
+  sample_rows_kernel<<<B, 256, 0, stream>>>((const uint16_t*)logits, V, p, out_ids);
   return CFC_CHECK_LAUNCH();
 }
 
