@@ -24,6 +24,7 @@ import json
 import math
 import os
 from pathlib import Path
+from typing import Any, NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -534,6 +535,20 @@ def argmax_keys(local: torch.Tensor, offset: int) -> torch.Tensor:
     return ((ku - 2 ** 31) << 32) | (0xFFFFFFFF - (i.to(torch.int64) + offset))
 
 
+class DecodeStep(NamedTuple):
+    """What one forward_decode call was given besides the token ids: built once per step and
+    handed to the layer loop and to _rope_attention, so that nothing per-step lives on the model
+    (a prefill worker and a decoding thread may run on one model at the same time)."""
+    positions: torch.Tensor
+    slots: torch.Tensor
+    ctx_lens: torch.Tensor
+    block_tables: torch.Tensor
+    kv: Any
+    attn_workspace: Any
+    part_blocks: int
+    shared_blocks: torch.Tensor | None
+
+
 class DecoderModel:
     """Stateless forward functions over :class:`DecoderWeights` + a paged KV cache."""
 
@@ -591,11 +606,11 @@ class DecoderModel:
         # per CU, which costs more than the 10.6-us rope_kv launch it removes.  At B = 1 the launch
         # is the larger cost: 296.5 -> 299.9 tok/s Mistral-7B (profiles/r04_latprof_*).
         self.rope_fused = os.environ.get("CFC_DECODE_ROPE_FUSED", "")
-        # B <= 4 over packed weights: residual + RMSNorm folded into the next GEMV (K.gemv_norm).
-        # Opt-in: bit-identical, two launches fewer per layer, but slower -- the prologue's slab reads
-        # (written by another XCD, served from the MALL) stall the weight stream behind them:
-        # Mistral-7B 307.7 vs 313.5 tok/s, Llama-2-13B 177.1 vs 190.9 (profiles/r04_gemv_norm_ab.log)
-        self.gemv_norm_fused = os.environ.get("CFC_DECODE_GEMV_NORM", "0") == "1"
+        # retired: residual + RMSNorm folded into the next GEMV's prologue, bit-identical and measured
+        # slower on every model (profiles/ROOFLINE.md, "Rejected"); asking for it is an error, not a no-op
+        if os.environ.get("CFC_DECODE_GEMV_NORM", "0") not in ("", "0"):
+            raise ValueError(f"CFC_DECODE_GEMV_NORM={os.environ['CFC_DECODE_GEMV_NORM']!r}: the folded-norm GEMV was "
+                             "removed (measured slower); unset it or set 0")
         # TP > 1: the row-parallel (o / down) partials are all-reduced in fp32 and rounded to bf16
         # ONCE, as TP = 1 rounds the full sum (CFC_TP_AR_DTYPE=fp32, default); "bf16" rounds each
         # rank's partial first and halves the prefill all-reduce bytes (round 5's behaviour).  The
@@ -977,92 +992,22 @@ class DecoderModel:
             return "splitk"
         return "lib"
 
-    def _forward_decode_qgemm(self, x, positions, slots, ctx_lens, block_tables, kv, attn_workspace, part_blocks):
-        """4 < B <= qgemm_max_m decode straight from the GGUF blocks on the quantized decode GEMM
-        (qdgemm.hip: 3.6x / 2.4x fewer weight bytes than the bf16 copy at Q4_K / Q6_K).  Structure and rounding
-        points of _forward_decode_fused: qkv slabs (q, k, v fill one buffer with a shared split:
-        their ggml types may differ) -> RoPE / KV write / attention -> o slabs -> residual + RMSNorm
-        reduce -> gate and up slabs, interleaved 8 by 8 -> SwiGLU reduce -> down slabs -> residual +
-        RMSNorm reduce.  A projection without a quantized copy, or one the kernel does not take, runs
-        on the bf16 copy of that layer (decode GEMM, or the library when that is the decode mode)."""
-        cfg, w = self.cfg, self.w
-        B, eps, dev = x.shape[0], cfg.rms_eps, x.device
-        qs, ks = w.heads * cfg.head_dim, w.kv_heads * cfg.head_dim
-        residual = x.clone()
-        h = K.rmsnorm(x, w.layers[0]["attn_norm"], eps)
-        s_o = K.lib_split_for(qs, cfg.hidden)
-        s_d = K.lib_split_for(w.ffn, cfg.hidden)
-
-        def ok(*qws):
-            return all(q is not None and K.qdgemm_ok(B, q) for q in qws)
-
-        def slabs(split, n):
-            return K._workspace(dev, split * B * n)[:split * B * n].view(split, B, n)
-
-        for i in range(cfg.layers):
-            lw, ql = w.layers[i], w.qlayers[i]
-            if ok(ql["q"], ql["k"], ql["v"]) and qs % 4 == 0 and ks % 4 == 0:
-                bn, split = K.qdgemm_config(B, qs, cfg.hidden, ql["q"].qtype)     # q's launch: the widest
-                split = self.qkv_split or split
-                qkv = slabs(split, qs + 2 * ks)
-                K.qdgemm(h, ql["q"], "part", out=qkv, col0=0, bn=bn)
-                K.qdgemm(h, ql["k"], "part", out=qkv, col0=qs, bn=bn)
-                K.qdgemm(h, ql["v"], "part", out=qkv, col0=qs + ks, bn=bn)
-            elif self.fused_decode:
-                wq = self._decode_weight(i, "qkv")
-                qbn, qsplit = K.dgemm_config(B, wq.shape[0], h.shape[1], bn=getattr(wq, "bn", None))
-                qsplit = self.qkv_split or qsplit
-                qkv = K.dgemm(h, wq, "part", qsplit, bn=qbn) if qsplit > 1 else K.dgemm_linear(h, wq)
-            else:
-                qkv = F.linear(h, lw["qkv"])
-            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                        part_blocks)
-            a2 = attn.view(B, -1)
-            if ok(ql["o"]):
-                h = K.splitk_residual_rmsnorm(K.qdgemm(a2, ql["o"], "part"), residual, lw["mlp_norm"], eps)
-            elif self.fused_decode:
-                h = K.dgemm_residual_rmsnorm(a2, self._decode_weight(i, "o"), residual, lw["mlp_norm"], eps)
-            else:
-                h = K.lib_splitk_linear_residual_rmsnorm(a2, lw["o"], s_o, residual, lw["mlp_norm"], eps)
-            g, u = ql["gate"], ql["up"]
-            if ok(g, u) and g.N == u.N and g.N % 8 == 0:
-                bn, split = K.qdgemm_config(B, g.N, cfg.hidden, g.qtype)      # per launch: gate, then up
-                gu = slabs(split, 2 * g.N)
-                K.qdgemm(h, g, "part", out=gu, interleave="gate", bn=bn)
-                K.qdgemm(h, u, "part", out=gu, interleave="up", bn=bn)
-                a = K.splitk_reduce(gu, swiglu=True)
-            elif self.fused_decode:
-                a = K.dgemm_swiglu(h, self._decode_weight(i, "gate_up"))
-            else:
-                a = K.silu_mul(F.linear(h, lw["gate_up"]), interleaved=w.gate_up_interleaved)
-            nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
-            if ok(ql["down"]):
-                h = K.splitk_residual_rmsnorm(K.qdgemm(a, ql["down"], "part"), residual, nxt, eps)
-            elif self.fused_decode:
-                h = K.dgemm_residual_rmsnorm(a, self._decode_weight(i, "down"), residual, nxt, eps)
-            else:
-                h = K.lib_splitk_linear_residual_rmsnorm(a, lw["down"], s_d, residual, nxt, eps)
-        return h
-
     def forward_decode(self, ids, positions, slots, ctx_lens, block_tables, kv, attn_workspace=None,
                        part_blocks=16, shared_blocks=None) -> torch.Tensor:
         """One token per sequence. Returns final-normed hidden [B, H].  ``shared_blocks`` (device int32
         [1]): leading KV blocks every sequence shares (prefix cache) -- the attention reads them through
-        the caches instead of nontemporal."""
-        self._shared_blocks = shared_blocks
+        the caches instead of nontemporal.  decode_path() alone decides what the step runs on: an
+        optional quantized kernel family over a bf16 base family (_decode_layers), or the library
+        loop below (CPU, fp8, TP's fp32 partial carry)."""
         cfg, w = self.cfg, self.w
+        step = DecodeStep(positions, slots, ctx_lens, block_tables, kv, attn_workspace, part_blocks, shared_blocks)
         x = K.embedding(w.embed, ids)
         B = ids.shape[0]
         path = self.decode_path(B, x.is_cuda)
-        if path == "qgemm":
-            return self._forward_decode_qgemm(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                              part_blocks)
-        if path in ("dgemm", "scratch"):
-            return self._forward_decode_fused(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                              part_blocks)
-        if path != "lib":     # "qgemv" / "gemv" / "splitk": _forward_decode_splitk picks by the same rule
-            return self._forward_decode_splitk(x, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                               part_blocks)
+        if path != "lib":
+            base = {"qgemm": "dgemm" if self.fused_decode else "splitk",
+                    "qgemv": "dgemm" if w.quant_only else "gemv", "scratch": "dgemm"}.get(path, path)
+            return self._decode_layers(x, step, path if path in ("qgemv", "qgemm") else None, base)
         residual = None
         x32 = None
         for i in range(cfg.layers):
@@ -1072,8 +1017,7 @@ class DecoderModel:
             else:
                 h, residual = self._layer_pre(i, x, residual)
             qkv = self._lin(i, "qkv", h)
-            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                        part_blocks)
+            attn = self._rope_attention(i, qkv, step)
             if self.tp_fp32:
                 h = self._tp_norm(self._lin32(i, "o", attn.view(B, -1)), residual, lw["mlp_norm"])
                 gu = self._lin(i, "gate_up", h)
@@ -1085,67 +1029,149 @@ class DecoderModel:
             return self._tp_norm(x32, residual, w.final_norm)
         return K.rmsnorm(x, w.final_norm, cfg.rms_eps, residual=residual)
 
-    def _rope_attention(self, i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace, part_blocks):
+    def _rope_attention(self, i, qkv, step: DecodeStep):
         """RoPE + K/V cache write + paged decode attention of layer ``i`` from the qkv projection output
         (bf16 [B, N], or fp32 split-K slabs [split, B, N]).  Default: ONE kernel (the attention's
         prologue does the RoPE / KV write, ``CFC_DECODE_ROPE_FUSED=1``); else rope_kv then attention.
         Both write the same cache bytes and return the same output."""
-        cfg, w = self.cfg, self.w
-        sb = getattr(self, "_shared_blocks", None)
+        cfg, w, kv = self.cfg, self.w, step.kv
         B = qkv.shape[-2]
         fused = self.rope_fused == "1" or (self.rope_fused == "" and B <= K.GEMV_MAX_M)
         if fused and qkv.is_cuda:
-            return K.paged_decode_rope_attention(qkv, positions, slots, w.cos_sin, kv.k[i], kv.v[i], block_tables,
-                                                 ctx_lens, self.scale, w.heads, w.kv_heads, cfg.head_dim,
-                                                 part_blocks=part_blocks, workspace=attn_workspace,
-                                                 window=self.window, k_scale=kv.k_scale, v_scale=kv.v_scale,
-                                                 shared_blocks=sb)
-        if qkv.dim() == 3:
-            q = K.rope_kv_write_part(qkv, positions, slots, w.cos_sin, kv.k[i], kv.v[i], w.heads, w.kv_heads,
-                                     cfg.head_dim, k_scale=kv.k_scale, v_scale=kv.v_scale)
-        else:
-            q = K.rope_kv_write(qkv, positions, slots, w.cos_sin, kv.k[i], kv.v[i], w.heads, w.kv_heads,
-                                cfg.head_dim, k_scale=kv.k_scale, v_scale=kv.v_scale)
-        return K.paged_decode_attention(q, kv.k[i], kv.v[i], block_tables, ctx_lens, self.scale,
-                                        part_blocks=part_blocks, workspace=attn_workspace, window=self.window,
-                                        k_scale=kv.k_scale, v_scale=kv.v_scale, shared_blocks=sb)
+            return K.paged_decode_rope_attention(qkv, step.positions, step.slots, w.cos_sin, kv.k[i], kv.v[i],
+                                                 step.block_tables, step.ctx_lens, self.scale, w.heads, w.kv_heads,
+                                                 cfg.head_dim, part_blocks=step.part_blocks,
+                                                 workspace=step.attn_workspace, window=self.window,
+                                                 k_scale=kv.k_scale, v_scale=kv.v_scale,
+                                                 shared_blocks=step.shared_blocks)
+        rope = K.rope_kv_write_part if qkv.dim() == 3 else K.rope_kv_write
+        q = rope(qkv, step.positions, step.slots, w.cos_sin, kv.k[i], kv.v[i], w.heads, w.kv_heads, cfg.head_dim,
+                 k_scale=kv.k_scale, v_scale=kv.v_scale)
+        return K.paged_decode_attention(q, kv.k[i], kv.v[i], step.block_tables, step.ctx_lens, self.scale,
+                                        part_blocks=step.part_blocks, workspace=step.attn_workspace,
+                                        window=self.window, k_scale=kv.k_scale, v_scale=kv.v_scale,
+                                        shared_blocks=step.shared_blocks)
 
-    def _forward_decode_fused(self, x, positions, slots, ctx_lens, block_tables, kv, attn_workspace, part_blocks):
-        """Decode layer on the hand-written decode GEMM (dgemm.hip), elementwise work in epilogues:
-        qkv -> RoPE/KV write -> attention -> [o + residual + mlp RMSNorm] -> [gate_up + SwiGLU] ->
-        [down + residual + next layer's RMSNorm].  Same rounding points as the library path.
-        With TP the row-parallel o/down outputs are all-reduced (one-shot IPC all-reduce inside the
-        decode graph when available) before the residual + RMSNorm."""
+    def _decode_layers(self, x, step: DecodeStep, quant: str | None, base: str):
+        """The decode layer, elementwise work in the projections' epilogues and reduces:
+        qkv -> RoPE / KV write / attention -> [o + residual + mlp RMSNorm] -> [gate_up + SwiGLU] ->
+        [down + residual + next layer's RMSNorm], the same rounding points on every kernel family.
+        Each of the three projection roles (``_<family>_qkv``, ``_<family>_row`` for o and down,
+        ``_<family>_gate_up``) runs on the ``quant`` family ("qgemv", "qgemm" or None) where that
+        takes the projection -- it returns None where it does not: no quantized copy, a shape or a
+        type pairing its kernel refuses -- and otherwise on the ``base`` family ("dgemm", "gemv" or
+        "splitk") over the bf16 weights of the same layer."""
         cfg, w = self.cfg, self.w
         B = x.shape[0]
-        eps = cfg.rms_eps
         residual = x.clone()
-        h = K.rmsnorm(x, w.layers[0]["attn_norm"], eps)
-        tp = w.tp_size > 1
+        h = K.rmsnorm(x, w.layers[0]["attn_norm"], cfg.rms_eps)
+
+        roles = {r: (getattr(self, f"_{quant}_{r}") if quant else None, getattr(self, f"_{base}_{r}"))
+                 for r in ("qkv", "row", "gate_up")}
+
+        def run(role, *args):
+            q, b = roles[role]
+            out = q(*args) if q else None
+            return out if out is not None else b(*args)
+
         for i in range(cfg.layers):
-            lw = w.layers[i]
-            # fragment-packed copies when present; quantized-blocks-only weights: the one scratch,
-            # unpacked for each projection right before its GEMM (so fetched in order of use)
-            wq = self._decode_weight(i, "qkv")
-            qbn, qsplit = K.dgemm_config(B, wq.shape[0], h.shape[1], bn=getattr(wq, "bn", None))
-            qsplit = self.qkv_split or qsplit
-            # split-K slabs go straight into RoPE / KV write (the reduce folded in)
-            qkv = K.dgemm(h, wq, "part", qsplit, bn=qbn) if qsplit > 1 else K.dgemm_linear(h, wq)
-            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                        part_blocks)
-            wo = self._decode_weight(i, "o")
-            if tp:
-                h = self._tp_residual_rmsnorm(attn.view(B, -1), wo, residual, lw["mlp_norm"], eps)
-            else:
-                h = K.dgemm_residual_rmsnorm(attn.view(B, -1), wo, residual, lw["mlp_norm"], eps)
-            a = K.dgemm_swiglu(h, self._decode_weight(i, "gate_up"))
+            attn = self._rope_attention(i, run("qkv", i, h), step)
+            h = run("row", i, "o", attn.view(B, -1), residual, w.layers[i]["mlp_norm"])
+            a = run("gate_up", i, h)
             nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
-            wd = self._decode_weight(i, "down")
-            if tp:
-                h = self._tp_residual_rmsnorm(a, wd, residual, nxt, eps)
-            else:
-                h = K.dgemm_residual_rmsnorm(a, wd, residual, nxt, eps)
+            h = run("row", i, "down", a, residual, nxt)
         return h
+
+    # -- quantized GEMV (B <= 4, quant.hip): straight from the GGUF blocks, Q4_K / Q6_K / Q8_0 weight
+    # stream (3.6x fewer bytes than bf16 at Q4_K).  A projection takes it only when B rows of its
+    # input fit the kernel's LDS stage (K.qgemv_fits)
+
+    def _qgemv_qkv(self, i, h):
+        w, ql, B = self.w, self.w.qlayers[i], h.shape[0]
+        if ql["q"] is None or ql["k"] is None or ql["v"] is None or not K.qgemv_fits(B, h.shape[1]):
+            return None
+        qs, ks = w.heads * self.cfg.head_dim, w.kv_heads * self.cfg.head_dim
+        qkv = torch.empty(B, qs + 2 * ks, dtype=torch.bfloat16, device=h.device)
+        ld = qkv.shape[1]   # q, k, v write their column slices (types may differ: Q4_K_M's v is often Q6_K)
+        K.qgemv(h, ql["q"], out=qkv, ldo=ld)
+        K.qgemv(h, ql["k"], out=qkv[:, qs:], ldo=ld)
+        K.qgemv(h, ql["v"], out=qkv[:, qs + ks:], ldo=ld)
+        return qkv
+
+    def _qgemv_row(self, i, name, x, residual, norm_w):
+        qw, B, H = self.w.qlayers[i][name], x.shape[0], self.cfg.hidden
+        if qw is None or not K.qgemv_fits(B, x.shape[1]):
+            return None
+        part = K._workspace(x.device, B * H)[:B * H].view(1, B, H)
+        K.qgemv(x, qw, "f32", out=part[0])
+        return K.splitk_residual_rmsnorm(part, residual, norm_w, self.cfg.rms_eps)
+
+    def _qgemv_gate_up(self, i, h):
+        g, u = self.w.qlayers[i]["gate"], self.w.qlayers[i]["up"]
+        if g is None or u is None or g.qtype != u.qtype or not K.qgemv_fits(h.shape[0], h.shape[1]):
+            return None
+        return K.qgemv(h, g, "swiglu", qw2=u)
+
+    # -- quantized decode GEMM (4 < B <= qgemm_max_m, qdgemm.hip: 3.6x / 2.4x fewer weight bytes than
+    # the bf16 copy at Q4_K / Q6_K): fp32 split-K slabs into the consumers the bf16 decode GEMM feeds
+
+    def _qgemm_ok(self, B, *qws):
+        return all(q is not None and K.qdgemm_ok(B, q) for q in qws)
+
+    @staticmethod
+    def _slabs(like, split, n):
+        B = like.shape[0]
+        return K._workspace(like.device, split * B * n)[:split * B * n].view(split, B, n)
+
+    def _qgemm_qkv(self, i, h):
+        w, ql, B = self.w, self.w.qlayers[i], h.shape[0]
+        qs, ks = w.heads * self.cfg.head_dim, w.kv_heads * self.cfg.head_dim
+        if not (self._qgemm_ok(B, ql["q"], ql["k"], ql["v"]) and qs % 4 == 0 and ks % 4 == 0):
+            return None
+        # q, k, v fill one buffer with a shared split (their ggml types may differ): q's launch, the widest
+        bn, split = K.qdgemm_config(B, qs, self.cfg.hidden, ql["q"].qtype)
+        qkv = self._slabs(h, self.qkv_split or split, qs + 2 * ks)
+        K.qdgemm(h, ql["q"], "part", out=qkv, col0=0, bn=bn)
+        K.qdgemm(h, ql["k"], "part", out=qkv, col0=qs, bn=bn)
+        K.qdgemm(h, ql["v"], "part", out=qkv, col0=qs + ks, bn=bn)
+        return qkv
+
+    def _qgemm_row(self, i, name, x, residual, norm_w):
+        qw = self.w.qlayers[i][name]
+        if not self._qgemm_ok(x.shape[0], qw):
+            return None
+        return K.splitk_residual_rmsnorm(K.qdgemm(x, qw, "part"), residual, norm_w, self.cfg.rms_eps)
+
+    def _qgemm_gate_up(self, i, h):
+        g, u = self.w.qlayers[i]["gate"], self.w.qlayers[i]["up"]
+        if not (self._qgemm_ok(h.shape[0], g, u) and g.N == u.N and g.N % 8 == 0):
+            return None
+        bn, split = K.qdgemm_config(h.shape[0], g.N, self.cfg.hidden, g.qtype)      # per launch: gate, then up
+        gu = self._slabs(h, split, 2 * g.N)                                        # interleaved 8 by 8
+        K.qdgemm(h, g, "part", out=gu, interleave="gate", bn=bn)
+        K.qdgemm(h, u, "part", out=gu, interleave="up", bn=bn)
+        return K.splitk_reduce(gu, swiglu=True)
+
+    # -- bf16 decode GEMM (dgemm.hip) over _decode_weight: the fragment-packed copy, the row-major
+    # one, or the quantized-blocks-only scratch, unpacked for each projection right before its GEMM
+    # (so fetched in order of use).  With TP the row-parallel o / down outputs are all-reduced
+    # (one-shot IPC all-reduce inside the decode graph when available) before the residual + RMSNorm
+
+    def _dgemm_qkv(self, i, h):
+        wq = self._decode_weight(i, "qkv")
+        qbn, qsplit = K.dgemm_config(h.shape[0], wq.shape[0], h.shape[1], bn=getattr(wq, "bn", None))
+        qsplit = self.qkv_split or qsplit
+        # split-K slabs go straight into RoPE / KV write (the reduce folded in)
+        return K.dgemm(h, wq, "part", qsplit, bn=qbn) if qsplit > 1 else K.dgemm_linear(h, wq)
+
+    def _dgemm_row(self, i, name, x, residual, norm_w):
+        wt = self._decode_weight(i, name)
+        if self.w.tp_size > 1:
+            return self._tp_residual_rmsnorm(x, wt, residual, norm_w, self.cfg.rms_eps)
+        return K.dgemm_residual_rmsnorm(x, wt, residual, norm_w, self.cfg.rms_eps)
+
+    def _dgemm_gate_up(self, i, h):
+        return K.dgemm_swiglu(h, self._decode_weight(i, "gate_up"))
 
     def _tp_residual_rmsnorm(self, x, w, residual, norm_w, eps):
         """Row-parallel projection + all-reduce + residual + RMSNorm at TP > 1 with TP = 1's
@@ -1158,152 +1184,35 @@ class DecoderModel:
         bn, split = K.dgemm_config(B, w.shape[0], Kd, bn=getattr(w, "bn", None))
         return self._tp_norm(K.dgemm(x, w, "part", split, bn=bn), residual, norm_w)
 
-    def _forward_decode_splitk(self, x, positions, slots, ctx_lens, block_tables, kv, attn_workspace, part_blocks):
-        """Library GEMMs; o and down as batched split-K with residual + next RMSNorm in the reduce."""
-        cfg, w = self.cfg, self.w
-        B = x.shape[0]
-        eps = cfg.rms_eps
-        residual = x.clone()
-        h = K.rmsnorm(x, w.layers[0]["attn_norm"], eps)
-        s_o = K.lib_split_for(w.heads * cfg.head_dim, cfg.hidden)
-        s_d = K.lib_split_for(w.ffn, cfg.hidden)
-        if self.decode_qgemv and B <= K.GEMV_MAX_M:
-            return self._forward_decode_qgemv(h, residual, positions, slots, ctx_lens, block_tables, kv,
-                                              attn_workspace, part_blocks)
-        if self.decode_gemv and B <= K.GEMV_MAX_M:
-            return self._forward_decode_gemv(h, residual, positions, slots, ctx_lens, block_tables, kv,
-                                             attn_workspace, part_blocks)
-        for i in range(cfg.layers):
-            lw = w.layers[i]
-            qkv = F.linear(h, lw["qkv"])
-            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                        part_blocks)
-            h = K.lib_splitk_linear_residual_rmsnorm(attn.view(B, -1), lw["o"], s_o, residual, lw["mlp_norm"], eps)
-            a = K.silu_mul(F.linear(h, lw["gate_up"]), interleaved=w.gate_up_interleaved)
-            nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
-            h = K.lib_splitk_linear_residual_rmsnorm(a, lw["down"], s_d, residual, nxt, eps)
-        return h
+    # -- bf16 GEMV (B <= 4, gemm.hip): gemv_tile_kernel over the packed copy when it is the only one
+    # (qkv as k-slice slabs straight into the slab-reading RoPE / KV write), gemv_kernel over the
+    # row-major weights; SwiGLU in the gate/up GEMV's epilogue
 
-    def _forward_decode_gemv(self, h, residual, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                             part_blocks):
-        """Single-stream / small-batch decode (B <= 4): every projection on the weight-streaming GEMV
-        kernel (gemm.hip: gemv_kernel), SwiGLU in the gate/up GEMV's epilogue, o and down feeding the
-        residual + next-RMSNorm reduce.  Same rounding points as _forward_decode_splitk."""
-        cfg, w = self.cfg, self.w
-        B, eps = h.shape[0], cfg.rms_eps
-        if w.packed_only and h.is_cuda and self.gemv_norm_fused and cfg.hidden <= 8192:
-            return self._forward_decode_gemv_fused(h, residual, positions, slots, ctx_lens, block_tables, kv,
-                                                   attn_workspace, part_blocks)
-        for i in range(cfg.layers):
-            # packed-only weights: the packed-weight GEMV reads the packed copies
-            lw = w.layers[i]
-            if w.packed_only:
-                lw = dict(lw, **w.packed[i])
-            # packed qkv: k-slice slabs straight into the slab-reading RoPE / KV write
-            qkv = K.gemv_part(h, lw["qkv"]) if isinstance(lw["qkv"], K.PackedWeight) else K.gemv(h, lw["qkv"])
-            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                        part_blocks)
-            h = K.gemv_residual_rmsnorm(attn.view(B, -1), lw["o"], residual, lw["mlp_norm"], eps)
-            a = K.gemv(h, lw["gate_up"], "swiglu")
-            nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
-            h = K.gemv_residual_rmsnorm(a, lw["down"], residual, nxt, eps)
-        return h
+    def _gemv_weight(self, i, name):
+        return (self.w.packed[i] if self.w.packed_only else self.w.layers[i])[name]
 
-    def _forward_decode_gemv_fused(self, h, residual, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                   part_blocks):
-        """B <= 4 decode over the packed weights with the residual + RMSNorm reduces folded into the
-        next GEMV's prologue (K.gemv_norm): per layer qkv (slabs, its input norm fused from the
-        previous down's slabs) -> RoPE / attention -> o (slabs) -> gate_up + SwiGLU (its input norm
-        fused from o's slabs) -> down (slabs).  Two launches fewer per layer than
-        _forward_decode_gemv, bit-identical to it: the prologue repeats the reduce kernel's
-        arithmetic.  The residual alternates between two buffers (a fused norm reads one while its
-        workgroup 0 writes the other); consecutive slab producers alternate two halves of the
-        split-K workspace (a producer's input slabs are still being read while it writes)."""
-        cfg, w = self.cfg, self.w
-        B, eps = h.shape[0], cfg.rms_eps
-        P = [w.packed[i] for i in range(cfg.layers)]
+    def _gemv_qkv(self, i, h):
+        wt = self._gemv_weight(i, "qkv")
+        return K.gemv_part(h, wt) if isinstance(wt, K.PackedWeight) else K.gemv(h, wt)
 
-        def nslab(W):
-            return K.gemv_packed_config(W.N, W.K, W.bn // 16, B)[0] * B * W.N
-        size = max(nslab(P[0][k]) for k in ("qkv", "o", "down"))
-        ws = K._workspace(h.device, 2 * size)
-        bufs, nb = (ws[:size], ws[size:2 * size]), 0
-        res, cur = (residual, torch.empty_like(residual)), 0
-        pend = None
-        for i in range(cfg.layers):
-            lw, pw = w.layers[i], P[i]
+    def _gemv_row(self, i, name, x, residual, norm_w):
+        return K.gemv_residual_rmsnorm(x, self._gemv_weight(i, name), residual, norm_w, self.cfg.rms_eps)
 
-            def out(W):
-                sp = K.gemv_packed_config(W.N, W.K, W.bn // 16, B)[0]
-                return bufs[nb][:sp * B * W.N].view(sp, B, W.N)
-            if pend is None:
-                qkv = K.gemv_part(h, pw["qkv"], out=out(pw["qkv"]))
-            else:
-                qkv = K.gemv_norm(pend, res[cur], res[1 - cur], lw["attn_norm"], eps, pw["qkv"], out=out(pw["qkv"]))
-                cur ^= 1
-            nb ^= 1
-            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                        part_blocks)
-            o = K.gemv_part(attn.view(B, -1), pw["o"], out=out(pw["o"]))
-            nb ^= 1
-            a = K.gemv_norm(o, res[cur], res[1 - cur], lw["mlp_norm"], eps, pw["gate_up"], "swiglu")
-            cur ^= 1
-            pend = K.gemv_part(a, pw["down"], out=out(pw["down"]))
-            nb ^= 1
-        return K.splitk_residual_rmsnorm(pend, res[cur], w.final_norm, eps)
+    def _gemv_gate_up(self, i, h):
+        return K.gemv(h, self._gemv_weight(i, "gate_up"), "swiglu")
 
-    def _forward_decode_qgemv(self, h, residual, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                              part_blocks):
-        """B <= 4 decode straight from the GGUF blocks (Q4_K / Q6_K / Q8_0 weight stream, 3.6x fewer
-        bytes than bf16 at Q4_K).  Projections without a quantized copy use the bf16 GEMV
-        (quantized-blocks-only weights: the bf16 decode GEMM on the unpack scratch).  Same rounding
-        points as _forward_decode_gemv."""
-        cfg, w = self.cfg, self.w
-        B, eps = h.shape[0], cfg.rms_eps
-        qs, ks = w.heads * cfg.head_dim, w.kv_heads * cfg.head_dim
-        for i in range(cfg.layers):
-            lw, ql = w.layers[i], w.qlayers[i]
-            # a projection takes its quantized copy only when B rows of its input fit the qgemv's
-            # LDS stage (K.qgemv_fits); otherwise the bf16 GEMV of the same layer
-            fit_h, fit_o, fit_d = K.qgemv_fits(B, cfg.hidden), K.qgemv_fits(B, qs), K.qgemv_fits(B, w.ffn)
-            if ql["q"] is not None and ql["k"] is not None and ql["v"] is not None and fit_h:
-                qkv = torch.empty(B, qs + 2 * ks, dtype=torch.bfloat16, device=h.device)
-                ld = qkv.shape[1]   # q, k, v write their column slices (types may differ: Q4_K_M's v is often Q6_K)
-                K.qgemv(h, ql["q"], out=qkv, ldo=ld)
-                K.qgemv(h, ql["k"], out=qkv[:, qs:], ldo=ld)
-                K.qgemv(h, ql["v"], out=qkv[:, qs + ks:], ldo=ld)
-            elif w.quant_only:
-                qkv = K.dgemm_linear(h, self._scratch_weight(i, "qkv"))
-            else:
-                qkv = K.gemv(h, lw["qkv"])
-            attn = self._rope_attention(i, qkv, positions, slots, ctx_lens, block_tables, kv, attn_workspace,
-                                        part_blocks)
-            a2 = attn.view(B, -1)
-            if ql["o"] is not None and fit_o:
-                part = K._workspace(h.device, B * cfg.hidden)[:B * cfg.hidden].view(1, B, cfg.hidden)
-                K.qgemv(a2, ql["o"], "f32", out=part[0])
-                h = K.splitk_residual_rmsnorm(part, residual, lw["mlp_norm"], eps)
-            elif w.quant_only:
-                h = K.dgemm_residual_rmsnorm(a2, self._scratch_weight(i, "o"), residual, lw["mlp_norm"], eps)
-            else:
-                h = K.gemv_residual_rmsnorm(a2, lw["o"], residual, lw["mlp_norm"], eps)
-            g, u = ql["gate"], ql["up"]
-            if g is not None and u is not None and g.qtype == u.qtype and fit_h:
-                a = K.qgemv(h, g, "swiglu", qw2=u)
-            elif w.quant_only:
-                a = K.dgemm_swiglu(h, self._scratch_weight(i, "gate_up"))
-            else:
-                a = K.gemv(h, lw["gate_up"], "swiglu")
-            nxt = w.layers[i + 1]["attn_norm"] if i + 1 < cfg.layers else w.final_norm
-            if ql["down"] is not None and fit_d:
-                part = K._workspace(h.device, B * cfg.hidden)[:B * cfg.hidden].view(1, B, cfg.hidden)
-                K.qgemv(a, ql["down"], "f32", out=part[0])
-                h = K.splitk_residual_rmsnorm(part, residual, nxt, eps)
-            elif w.quant_only:
-                h = K.dgemm_residual_rmsnorm(a, self._scratch_weight(i, "down"), residual, nxt, eps)
-            else:
-                h = K.gemv_residual_rmsnorm(a, lw["down"], residual, nxt, eps)
-        return h
+    # -- library GEMMs; o and down as batched split-K with residual + next RMSNorm in the reduce
+
+    def _splitk_qkv(self, i, h):
+        return F.linear(h, self.w.layers[i]["qkv"])
+
+    def _splitk_row(self, i, name, x, residual, norm_w):
+        split = K.lib_split_for(x.shape[1], self.cfg.hidden)
+        return K.lib_splitk_linear_residual_rmsnorm(x, self.w.layers[i][name], split, residual, norm_w,
+                                                    self.cfg.rms_eps)
+
+    def _splitk_gate_up(self, i, h):
+        return K.silu_mul(F.linear(h, self.w.layers[i]["gate_up"]), interleaved=self.w.gate_up_interleaved)
 
     def greedy_ids(self, hidden: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """Greedy next tokens into ``out`` [B] int32 without gathering the logits: each vocab

@@ -304,6 +304,19 @@ def test_retired_prefill_gemm_variant_fails_at_model_construction(monkeypatch, v
         DecoderModel(DecoderWeights.random(cfg, "cpu", seed=0))
 
 
+def test_retired_gemv_norm_switch_fails_at_model_construction(monkeypatch):
+    """CFC_DECODE_GEMV_NORM=1 asked for a kernel that no longer exists: an error that names the
+    variable when the model is built; unset and 0 construct as before."""
+    cfg = get_config("tiny")
+    monkeypatch.setenv("CFC_DECODE_GEMV_NORM", "1")
+    with pytest.raises(ValueError, match="CFC_DECODE_GEMV_NORM"):
+        DecoderModel(DecoderWeights.random(cfg, "cpu", seed=0))
+    monkeypatch.setenv("CFC_DECODE_GEMV_NORM", "0")
+    DecoderModel(DecoderWeights.random(cfg, "cpu", seed=0))
+    monkeypatch.delenv("CFC_DECODE_GEMV_NORM")
+    DecoderModel(DecoderWeights.random(cfg, "cpu", seed=0))
+
+
 def test_prefill_tile_order_groups_sequences_by_l2_budget_heaviest_first_inside():
     """The prefill attention's tile order (ops.kernels.prefill_tiles with ctx_lens): consecutive
     sequences in groups of at most PREFILL_GROUP_CTX context tokens, groups in order, each group's
