@@ -132,7 +132,9 @@ class ContinuousEngine:
         # stop strings matched on the device (runtime/stops.py): a slot finishes at the token that
         # completes one, so the slot is freed and refilled instead of decoding to its limit
         self.stop_strings = stop_strings
-        self.stop_state = stop_strings.new_state(B, dev) if stop_strings is not None else None
+        # (the tables get a row for every id the model can sample, not only the tokenizer's)
+        self.stop_state = stop_strings.new_state(B, dev, self.model.cfg.vocab_size) \
+            if stop_strings is not None else None
         # rows of the logit processors' parameters and of the log-probability records: created with
         # the first step that needs them (the server sets ``sampling`` after construction)
         self.logit_state = None

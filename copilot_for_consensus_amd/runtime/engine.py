@@ -372,7 +372,8 @@ class LLMEngine:
             # persistent: a captured graph holds these pointers
             st.stop_ids = torch.tensor(list(stop_ids), dtype=torch.int32, device=self.device)
             if stop_strings is not None:
-                st.stop_state = stop_strings.new_state(B, self.device)
+                # the sampler returns model ids: the tables get a row for each, not only the tokenizer's
+                st.stop_state = stop_strings.new_state(B, self.device, self.cfg.vocab_size)
                 st.stop_matcher = stop_strings      # keeps id(stop_strings) in the key valid
             if lkey is not None:
                 st.logit_state = K.LogitState(B, self.device, self.penalty_window,

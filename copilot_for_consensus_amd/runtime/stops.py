@@ -10,8 +10,10 @@ generated text, L = the longest stop) and every sampled token is matched against
 
 From the tokenizer's per-token byte strings (``token_bytes``) this module builds, once per stop
 set, four device tables indexed by token id -- the first L bytes, the last L-1 bytes, the byte
-length, and whether a stop lies entirely inside the token -- which the decode-advance kernels
-(csrc/kernels/elementwise.hip: stop_feed) read.  A slot that matches is finished on the device, so
+length, and whether a stop lies entirely inside the token (bit 0: inside its bytes, bit 1: inside
+its bytes after the one leading space that decode() drops from a text's first bytes) -- which the
+decode-advance kernels (csrc/kernels/elementwise.hip: stop_feed) read.  The tables have a row for
+every id the model can sample: ids past the tokenizer's vocabulary are zero-length tokens.  A slot that matches is finished on the device, so
 the engine stops decoding it (the continuous engine frees and refills it) instead of generating all
 ``max_new`` tokens and cutting the text afterwards.  :meth:`StopStringMatcher.feed` is the host
 reference of the same automaton (the CPU path, the prefill's first token, and the tests).
@@ -50,8 +52,10 @@ class StopStringMatcher:
             head[v, :len(hb)] = np.frombuffer(hb, np.uint8)
             tb = b[-self.H:] if b else b""
             tail[v, :len(tb)] = np.frombuffer(tb, np.uint8)
-            # a stop entirely inside the token (checked on the token as it would appear mid-text)
-            contains[v] = any(s in b for s in self.stops)
+            # a stop entirely inside the token: bit 0 as the token appears mid-text, bit 1 as it
+            # appears at the start of a text that loses one leading space
+            lead = b[1:] if b[:1] == b" " else b
+            contains[v] = any(s in b for s in self.stops) | any(s in lead for s in self.stops) << 1
         self.tables = {"head": head, "tail": tail, "len": lens, "contains": contains}
         smat = np.zeros((len(self.stops), L), np.uint8)
         for i, s in enumerate(self.stops):
@@ -68,17 +72,31 @@ class StopStringMatcher:
         return cls(tokenizer.token_bytes, tokenizer.vocab_size, stops,
                    getattr(tokenizer, "strips_leading_space", False))
 
+    def cover_vocab(self, vocab_size: int) -> None:
+        """Give the tables a row for every id below ``vocab_size`` (a model whose embedding is
+        padded past the tokenizer's vocabulary can sample such ids): zero-length tokens."""
+        extra = int(vocab_size) - self.V
+        if extra <= 0:
+            return
+        self.tables = {k: np.concatenate([v, np.zeros((extra,) + v.shape[1:], v.dtype)])
+                       for k, v in self.tables.items()}
+        self._bytes += [b""] * extra
+        self.V += extra
+        self._dev = {}      # states made earlier keep the tables they were made with
+
     # ---------------------------------------------------------------- host reference
     def initial(self) -> tuple[bytes, bool]:
-        """Per-slot state: (last H bytes of the generated text, nothing generated yet)."""
+        """Per-slot state: (last H bytes of the generated text, no byte generated yet)."""
         return b"", True
 
     def feed(self, state: tuple[bytes, bool], tok: int) -> tuple[tuple[bytes, bool], bool]:
         win, fresh = state
-        b = self._bytes[tok] if 0 <= tok < self.V else b""
-        if fresh and self.strip and b[:1] == b" ":
-            b = b[1:]
-        hit = bool(self.tables["contains"][tok]) if 0 <= tok < self.V else False
+        raw = b = self._bytes[tok] if 0 <= tok < self.V else b""
+        # the text's first byte, when it is a space, is dropped as decode() does: once per text
+        lead = fresh and self.strip and raw[:1] == b" "
+        if lead:
+            b = raw[1:]
+        hit = bool(self.tables["contains"][tok] & (2 if lead else 1)) if raw else False
         if not hit and b:
             text = win + b
             for s in self.stops:
@@ -88,7 +106,7 @@ class StopStringMatcher:
                     hit = True
                     break
         text = win + b
-        return (text[-self.H:] if len(text) > self.H else text, fresh and not b), hit
+        return (text[-self.H:] if len(text) > self.H else text, fresh and not raw), hit
 
     def match_tokens(self, toks) -> int | None:
         """Index of the token that completes the first stop, or None (host reference)."""
@@ -109,13 +127,17 @@ class StopStringMatcher:
             self._dev[key] = d
         return self._dev[key]
 
-    def new_state(self, B: int, device) -> "StopState":
+    def new_state(self, B: int, device, vocab_size: int | None = None) -> "StopState":
+        """``vocab_size``: the number of ids the model can sample, when it may exceed the
+        tokenizer's vocabulary."""
+        if vocab_size is not None:
+            self.cover_vocab(vocab_size)
         return StopState(self, B, device)
 
 
 class StopState:
     """Per-slot device state of the matcher for one decode batch (static buffers a captured graph
-    reads and writes): window bytes [B, H], window length [B] (-1 = nothing generated yet, so a
+    reads and writes): window bytes [B, H], window length [B] (-1 = no byte generated yet, so a
     SentencePiece leading space can be dropped as decode() does), and ``keep`` [B] = tokens to keep
     (the count through the stop-completing token; ``cap`` while the slot runs on)."""
 

@@ -534,9 +534,11 @@ __global__ void __launch_bounds__(256) sample_rows_kernel(const uint16_t* __rest
 // Thread 0 of block 0 also bumps the device step counter.
 // Stop strings on the device (runtime/stops.py builds the tables): per token id the first L bytes
 // it adds to the decoded text, its last H = L - 1 bytes, its byte length and whether a stop lies
-// entirely inside it; per slot the last H bytes generated so far (wlen -1 = nothing yet, so a
-// SentencePiece leading space is dropped as decode() does) and `keep` = tokens through the
-// stop-completing one.  n_str == 0: no stop strings (the pointers are null).
+// entirely inside it (bit 0: inside its bytes; bit 1: inside its bytes without their leading
+// space); per slot the last H bytes generated so far (wlen -1 = no byte yet: the first token that
+// has bytes loses one leading space, as SentencePiece's decode() drops it, and ends that state
+// even when nothing remains of it) and `keep` = tokens through the stop-completing one.  The
+// tables have a row for every id the model samples.  n_str == 0: no stop strings (null pointers).
 struct StopTab {
   const uint8_t* head;
   const uint8_t* tail;
@@ -558,9 +560,10 @@ __device__ bool stop_feed(const StopTab& t, int b, int tok) {
   const bool fresh = wl < 0;
   if (fresh) wl = 0;
   const uint8_t* hd = t.head + (size_t)tok * t.L;
-  int n = t.tlen[tok], off = 0;
+  const int raw = t.tlen[tok];
+  int n = raw, off = 0;
   if (fresh && t.strip && n > 0 && hd[0] == ' ') { off = 1; n -= 1; }
-  bool hit = t.contains[tok] != 0;
+  bool hit = (t.contains[tok] & (off ? 2 : 1)) != 0;
   for (int s = 0; s < t.n_str && !hit; ++s) {
     const uint8_t* sp = t.stops + (size_t)s * t.L;
     const int ls = t.stop_lens[s];
@@ -582,7 +585,7 @@ __device__ bool stop_feed(const StopTab& t, int b, int tok) {
     for (int q = 0; q < n; ++q) w[kb + q] = hd[off + q];
     wl = kb + n;
   }
-  t.wlen[b] = (fresh && n == 0) ? -1 : wl;
+  t.wlen[b] = (fresh && raw == 0) ? -1 : wl;   // the one leading space is dropped once per text
   return hit;
 }
 
