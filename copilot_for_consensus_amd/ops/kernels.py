@@ -192,8 +192,23 @@ def rope_kv_write(qkv, positions, slots, cos_sin, k_cache, v_cache, Hq, Hkv, D, 
     return q_out
 
 
-def decode_partitions(max_ctx: int, part_blocks: int) -> int:
-    return max(1, math.ceil(math.ceil(max_ctx / KV_BLOCK) / part_blocks))
+def decode_workspace_numel(B: int, Hq: int, D: int, P: int) -> int:
+    """fp32 elements of the split-KV workspace: [B, Hq, P, D] partial outputs, then [B, Hq, P, 2]
+    (max, sum) pairs; nothing for P == 1 (the kernel writes ``out`` itself)."""
+    return B * Hq * P * (D + 2) if P > 1 else 0
+
+
+def _decode_plan(B, Hq, D, max_blocks, part_blocks, num_partitions, workspace, device):
+    """(part_blocks, P, part_o, part_ml) as the decode attention entry points take them (see
+    :func:`paged_decode_attention`); allocates the workspace P > 1 needs when none is given."""
+    if part_blocks < 0:          # -P: every sequence's own blocks split into P balanced ranges
+        num_partitions, part_blocks = -part_blocks, 0
+    if part_blocks == 0 and not num_partitions:
+        raise ValueError("balanced partitioning needs num_partitions (or part_blocks=-P)")
+    P = num_partitions or math.ceil(max_blocks / part_blocks)
+    if P > 1 and workspace is None:
+        workspace = torch.empty(decode_workspace_numel(B, Hq, D, P), dtype=torch.float32, device=device)
+    return (part_blocks, P, workspace, workspace[B * Hq * P * D:]) if P > 1 else (part_blocks, P, None, None)
 
 
 def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, out=None, part_blocks=16,
@@ -213,19 +228,9 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, o
     _req(block_tables, torch.int32, "block_tables")
     _req(ctx_lens, torch.int32, "ctx_lens")
     max_blocks = block_tables.shape[1]
-    if part_blocks < 0:          # -P: every sequence's own blocks split into P balanced ranges
-        num_partitions, part_blocks = -part_blocks, 0
-    if part_blocks == 0 and not num_partitions:
-        raise ValueError("balanced partitioning needs num_partitions (or part_blocks=-P)")
-    Pn = num_partitions or math.ceil(max_blocks / part_blocks)
+    part_blocks, Pn, part_o, part_ml = _decode_plan(B, Hq, D, max_blocks, part_blocks, num_partitions, workspace,
+                                                    q.device)
     out = torch.empty_like(q) if out is None else out
-    if Pn > 1:
-        if workspace is None:
-            workspace = torch.empty(B * Hq * Pn * (D + 2), dtype=torch.float32, device=q.device)
-        part_o = workspace
-        part_ml = workspace[B * Hq * Pn * D:]
-    else:
-        part_o = part_ml = None
     if _fp8(k_cache):
         check(kernels().cfc_paged_decode_attention_fp8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                                        block_tables.data_ptr(), ctx_lens.data_ptr(), B, Hq, Hkv, D,
@@ -278,17 +283,8 @@ def paged_decode_rope_attention(qkv, positions, slots, cos_sin, k_cache, v_cache
     if cos_sin.dtype != torch.float32 or tuple(cos_sin.shape[1:]) != (D // 2, 2) or not cos_sin.is_contiguous():
         raise ValueError("paged_decode_rope_attention: cos_sin must be fp32 [max_pos, D/2, 2]")
     max_blocks = block_tables.shape[1]
-    if part_blocks < 0:
-        Pn, part_blocks = -part_blocks, 0
-    else:
-        Pn = math.ceil(max_blocks / part_blocks)
+    part_blocks, Pn, part_o, part_ml = _decode_plan(B, Hq, D, max_blocks, part_blocks, None, workspace, qkv.device)
     out = torch.empty(B, Hq, D, dtype=torch.bfloat16, device=qkv.device) if out is None else out
-    if Pn > 1:
-        if workspace is None:
-            workspace = torch.empty(B * Hq * Pn * (D + 2), dtype=torch.float32, device=qkv.device)
-        part_o, part_ml = workspace, workspace[B * Hq * Pn * D:]
-    else:
-        part_o = part_ml = None
     check(kernels().cfc_paged_decode_rope_attention(
         qkv_p, part_p, split, positions.data_ptr(), slots.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(),
         v_cache.data_ptr(), block_tables.data_ptr(), ctx_lens.data_ptr(), B, Hq, Hkv, D, max_blocks, part_blocks, Pn,
@@ -297,18 +293,21 @@ def paged_decode_rope_attention(qkv, positions, slots, cos_sin, k_cache, v_cache
     return out
 
 
-PREFILL_TILE_ROWS = 128   # query rows per workgroup of the legacy single-head prefill kernels
+PREFILL_TILE_ROWS = 128   # query rows per prefill tile on the CPU path (the reference ignores tiles)
 ENCODER_TILE_ROWS = 256   # query rows per workgroup of the encoder attention kernel (attention.hip ENC_ROWS)
 
 
 def prefill_rows(Hq: int, Hkv: int) -> int:
-    """Query rows per tile the decoder prefill kernel expects: the default GQA-packed kernel takes
-    256 / G rows of all G = Hq / Hkv heads of one kv-head per workgroup (attention.hip:
-    prefill_gqa_kernel), the legacy kernels 128 rows of one head."""
-    lib = kernels() if torch.cuda.is_available() else None
-    if lib is None:
+    """Query rows per tile the decoder prefill kernel expects: 256 / G rows of all G = Hq / Hkv
+    heads of one kv-head per workgroup (attention.hip: prefill_gqa_kernel), G in {1, 2, 4, 8}."""
+    if (v := os.environ.get("CFC_PREFILL_VARIANT", "")) not in ("", "5"):     # retired: 0..3, single-head kernels
+        raise ValueError(f"CFC_PREFILL_VARIANT={v!r}: the legacy prefill attention kernels were removed")
+    if not torch.cuda.is_available():
         return PREFILL_TILE_ROWS
-    return int(lib.cfc_prefill_rows(int(Hq), int(Hkv)))
+    rows = int(kernels().cfc_prefill_rows(int(Hq), int(Hkv)))
+    if rows == 0:
+        raise ValueError(f"prefill attention: Hq={Hq}, Hkv={Hkv} has no kernel; Hq / Hkv must be 1, 2, 4 or 8")
+    return rows
 
 
 # context tokens of one group of sequences in the prefill attention's tile order: the grid gives each
@@ -344,7 +343,7 @@ def prefill_tiles(cu_q: list[int], tile: int = PREFILL_TILE_ROWS, ctx_lens: list
 def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, scale, tiles=None, out=None, window=0,
                       k_scale=1.0, v_scale=1.0):
     """q [T, Hq, D] (packed varlen); cu_q [S+1] int32; ctx_lens [S] int32 (cached + new);
-    ``window`` > 0: sliding-window attention (needs the GQA-packed kernel's G in {1, 2, 4, 8})."""
+    ``window`` > 0: sliding-window attention.  Hq / Hkv must be 1, 2, 4 or 8 (:func:`prefill_rows`)."""
     if not q.is_cuda:
         return ref.prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, scale, window=window,
                                      k_scale=k_scale, v_scale=v_scale)

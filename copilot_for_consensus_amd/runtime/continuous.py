@@ -145,7 +145,7 @@ class ContinuousEngine:
         # workspace per width.
         self.widths = sorted({w for w in (1, 2, 4, 8, 16, 32, 64) if w < B} | {B})
         self._pb = {w: engine._part_blocks(w, self.max_blocks) for w in self.widths}
-        ws = max(w * self.model.w.heads * -pb * (self.model.cfg.head_dim + 2) if -pb > 1 else 1
+        ws = max(K.decode_workspace_numel(w, self.model.w.heads, self.model.cfg.head_dim, -pb)
                  for w, pb in self._pb.items())
         self.workspace = torch.empty(max(1, ws), dtype=torch.float32, device=dev)
         self.part_blocks = self._pb[B]

@@ -367,7 +367,7 @@ class LLMEngine:
         st = self._states.get(key)
         if st is None:
             P = -part_blocks if part_blocks < 0 else math.ceil(max_blocks / part_blocks)
-            ws = B * self.model.w.heads * P * (self.cfg.head_dim + 2) if P > 1 else 1
+            ws = K.decode_workspace_numel(B, self.model.w.heads, self.cfg.head_dim, P)
             st = _DecodeState(B, max_blocks, max_new, self.device, ws)
             # persistent: a captured graph holds these pointers
             st.stop_ids = torch.tensor(list(stop_ids), dtype=torch.int32, device=self.device)

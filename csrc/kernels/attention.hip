@@ -119,7 +119,6 @@ struct DecRope {
   const int32_t* slots;    // -1: no cache write
   const float* cos_sin;
   float inv_k, inv_v;
-  int probe;               // timing ablations only (cfc_set_decode_rope_probe); 0 in production
 };
 
 // One KV block's K fragments (bf16: 8 x 16 B per lane; fp8: 4 x 16 B) and V^T fragments (8) of
@@ -249,7 +248,7 @@ __global__ void __launch_bounds__(256, F8 ? 2 : 1) paged_decode_kernel(
           *reinterpret_cast<uint4*>(&sm_q[hh][c * 8]) = pa;
           *reinterpret_cast<uint4*>(&sm_q[hh][D / 2 + c * 8]) = pb;
         } else {
-          if (!(rp.probe & 1)) kv_write_k<F8>(const_cast<void*>(kc), slot, h, Hkv, D, c, pa, pb, rp.inv_k);
+          kv_write_k<F8>(const_cast<void*>(kc), slot, h, Hkv, D, c, pa, pb, rp.inv_k);
           if constexpr (PATCH) {
             *reinterpret_cast<uint4*>(&sm_kv[0][c * 8]) = pa;
             *reinterpret_cast<uint4*>(&sm_kv[0][D / 2 + c * 8]) = pb;
@@ -299,24 +298,13 @@ __global__ void __launch_bounds__(256, F8 ? 2 : 1) paged_decode_kernel(
               for (int c = 0; c < 4; ++c) kr[st * 4 + c] = *reinterpret_cast<const uint4*>(&sm_kv[0][32 * c + 8 * g]);
         }
         // V^T column of key sn: stored at slot position ps = kv_v_slot(sn), i.e. element ps % 8 of
-        // the lanes g == ps / 8 (rows d = 16 dt + col)
+        // the lanes g == ps / 8 (rows d = 16 dt + col).  Those lanes then store the new key's slot
+        // group of the V^T tile back to the cache: their 8 x 16-byte pieces, the group's 16 full lines
         const int ps = kv_v_slot(sn);
         if (g == (ps >> 3)) {
+          uint16_t* vt = reinterpret_cast<uint16_t*>(const_cast<void*>(vc)) + ((size_t)bt[bi] * Hkv + h) * head_stride;
 #pragma unroll
           for (int dt = 0; dt < 8; ++dt) vr[dt] = set_bf16(vr[dt], ps & 7, sm_kv[1][16 * dt + col]);
-        }
-        // the new key's slot group of the V^T tile back to the cache: the lanes g == ps / 8 store
-        // their 8 x 16-byte pieces, the group's 16 full cache lines
-        uint16_t* vt = reinterpret_cast<uint16_t*>(const_cast<void*>(vc)) + ((size_t)bt[bi] * Hkv + h) * head_stride;
-        if (g != (ps >> 3)) {
-        } else if (rp.probe & 4) {
-#pragma unroll
-          for (int dt = 0; dt < 8; ++dt) {
-            const uint4 v = vr[dt];
-            __builtin_nontemporal_store(u32x4_t{v.x, v.y, v.z, v.w},
-                                        reinterpret_cast<u32x4_t*>(vt + kv_v_off(16 * dt + col, 8 * g, D)));
-          }
-        } else if (!(rp.probe & 2)) {
 #pragma unroll
           for (int dt = 0; dt < 8; ++dt) *reinterpret_cast<uint4*>(vt + kv_v_off(16 * dt + col, 8 * g, D)) = vr[dt];
         }
@@ -458,398 +446,16 @@ __global__ void __launch_bounds__(128) decode_combine_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------
-// Varlen causal prefill over the paged cache (D = 128).
-// grid = (n_tiles, Hq); block = 512 = 8 waves x 16 query rows = 128-row query tile.
-// Tile t covers query rows [tile_q0[t], +128) of sequence tile_seq[t]; those rows sit at
-// positions ctx - q_len + row (chunked prefill / prefix reuse: keys come from the cache).
-//   * K tile (64 keys x 128) and V^T tile (2 blocks x 128 x 32) double-buffered in LDS and shared
-//     by all 8 waves; register-staged (next tile's loads issue before this tile's MFMAs, LDS
-//     writes after -- guide §5.5 T14); one barrier per tile.
-//   * <= 128 VGPRs so two workgroups (16 waves, 4 per SIMD) share a CU: one wave's softmax VALU
-//     overlaps another's MFMAs (a 1-wave-per-SIMD build of this loop was VALU-serialised).
-//   * VALU trimmed: Q is pre-scaled by softmax_scale*log2(e) once (scores come out of the MFMA
-//     in the exp2 domain), the causal mask is applied only on tiles that cross the diagonal, and
-//     the O rescale is deferred until the running max grows by > RESCALE_THR (guide T13; P is
-//     then bounded by 2^THR, exact after the final 1/l).
-//   * The host orders tiles heaviest-first (most keys) so the causal triangle drains evenly.
-// ------------------------------------------------------------------------------------------
-constexpr int PF_KT = 64;     // keys per tile
-#ifndef CFC_PF_QK_PIPE
-#define CFC_PF_QK_PIPE 1
-#endif
-constexpr int PF_QK_PIPE = CFC_PF_QK_PIPE;
-#ifndef CFC_PF_V_EARLY
-#define CFC_PF_V_EARLY 1
-#endif
-constexpr int PF_V_EARLY = CFC_PF_V_EARLY;   // prefill v5: V fragments of the first PF_V_EARLY half-tiles read before the softmax (2: 251 VGPRs, 1 % slower, profiles/r05_ab_prefill_attn_vearly2_rejected.log)
-   // prefill v5: K fragments of a half-tile read ahead of its MFMAs
-constexpr int PF_WAVES = 8;
-constexpr int PF_ROWS = 16 * PF_WAVES;
-constexpr float RESCALE_THR = 8.0f;
-
-__device__ __forceinline__ int k_lds_off(int row, int ch) { return row * 256 + ((ch ^ (row & 15)) << 4); }
-__device__ __forceinline__ int v_lds_off(int blk, int d, int ch) {
-  return blk * 128 * 64 + d * 64 + ((ch ^ (((d >> 3) & 1) << 1)) << 4);
-}
-
-template <int MINW>
-__global__ void __launch_bounds__(512, MINW) prefill_paged_kernel(
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
-    const int32_t* __restrict__ block_tables, const int32_t* __restrict__ cu_q, const int32_t* __restrict__ ctx_lens,
-    const int32_t* __restrict__ tile_seq, const int32_t* __restrict__ tile_q0, float scale_log2, int Hq, int Hkv,
-    int max_blocks, uint16_t* __restrict__ out) {
-  constexpr int D = 128;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // LDS: [K buf0 16K][K buf1 16K][V buf0 16K][V buf1 16K]
-  const int t = blockIdx.x, hq = blockIdx.y;
-  const int G = Hq / Hkv, hk = hq / G;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tid = threadIdx.x;
-  const int col = lane & 15, g = lane >> 4;
-  const int s = tile_seq[t], qs = tile_q0[t];
-  const int q_begin = cu_q[s], q_len = cu_q[s + 1] - q_begin;
-  const int ctx = ctx_lens[s];
-  const int pos_base = ctx - q_len;
-  const int row_last = min(qs + PF_ROWS - 1, q_len - 1);
-  const int kend = pos_base + row_last + 1;  // keys [0, kend) are needed by this tile
-  const int ntiles = (kend + PF_KT - 1) / PF_KT;
-  const int32_t* bt = block_tables + (size_t)s * max_blocks;
-
-  const int my_row = qs + 16 * w + col;
-  const int my_pos = pos_base + my_row;
-  const int wave_min_pos = pos_base + qs + 16 * w;
-  bf16x8_t qf[4];
-  {
-    const int rr = min(my_row, q_len - 1);
-    const uint16_t* qr = q + ((size_t)(q_begin + rr) * Hq + hq) * D;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float f[8];
-      unpack8(*reinterpret_cast<const uint4*>(qr + 32 * c + 8 * g), f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] *= scale_log2;
-      qf[c] = as_bf16x8(pack8(f));
-    }
-  }
-
-  uint4 kst[2], vst[2];
-  auto gload = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int id = tid + 512 * i;
-      {  // K: row = id>>4 (key within tile), ch = id&15
-        const int row = id >> 4, ch = id & 15, key = kt * PF_KT + row;
-        if (key < kend) {
-          const int blk = bt[key / KV_BS];
-          kst[i] = *reinterpret_cast<const uint4*>(kc + (((size_t)blk * Hkv + hk) * KV_BS + (key % KV_BS)) * D + ch * 8);
-        } else {
-          kst[i] = make_uint4(0, 0, 0, 0);
-        }
-      }
-      {  // V^T: blk_i = id>>9, d = (id>>2)&127, ch = id&3
-        const int bi = id >> 9, d = (id >> 2) & 127, ch = id & 3;
-        const int key0 = kt * PF_KT + bi * KV_BS;
-        if (key0 < kend) {
-          const int blk = bt[key0 / KV_BS];
-          vst[i] = *reinterpret_cast<const uint4*>(vc + ((size_t)blk * Hkv + hk) * D * KV_BS + kv_v_off(d, 8 * ch, D));
-        } else {
-          vst[i] = make_uint4(0, 0, 0, 0);
-        }
-      }
-    }
-  };
-  auto lwrite = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int id = tid + 512 * i;
-      *reinterpret_cast<uint4*>(smem + buf * 16384 + k_lds_off(id >> 4, id & 15)) = kst[i];
-      *reinterpret_cast<uint4*>(smem + 32768 + buf * 16384 + v_lds_off(id >> 9, (id >> 2) & 127, id & 3)) = vst[i];
-    }
-  };
-
-  f32x4_t o[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  float m = -INFINITY, l = 0.f;
-
-  gload(0);
-  lwrite(0);
-  __syncthreads();
-  for (int kt = 0; kt < ntiles; ++kt) {
-    const int cur = kt & 1;
-    const bool more = kt + 1 < ntiles;
-    if (more) gload(kt + 1);
-
-    const char* kb = smem + cur * 16384;
-    const char* vb = smem + 32768 + cur * 16384;
-    const int key0 = kt * PF_KT;
-    // tiles wholly above this wave's rows (possible only in the last tiles): skip the math
-    if (key0 <= wave_min_pos + 15) {
-      f32x4_t sc[4];
-#pragma unroll
-      for (int st = 0; st < 4; ++st) {
-        sc[st] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        const int row = 16 * st + col;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          sc[st] = mfma16(as_bf16x8(*reinterpret_cast<const uint4*>(kb + k_lds_off(row, 4 * c + g))), qf[c], sc[st]);
-      }
-      if (key0 + PF_KT - 1 > wave_min_pos) {  // diagonal tile: causal mask
-#pragma unroll
-        for (int st = 0; st < 4; ++st)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (key0 + 16 * st + 4 * g + i > my_pos) sc[st][i] = -INFINITY;
-      }
-      float tmax = fmaxf(fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3])),
-                         fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
-      tmax = fmaxf(tmax, fmaxf(fmaxf(fmaxf(sc[2][0], sc[2][1]), fmaxf(sc[2][2], sc[2][3])),
-                               fmaxf(fmaxf(sc[3][0], sc[3][1]), fmaxf(sc[3][2], sc[3][3]))));
-      tmax = xor16_max(tmax);
-      tmax = xor32_max(tmax);
-      // deferred rescale: keep the old max unless some row of the wave grew by > THR
-      if (!__all(tmax - m <= RESCALE_THR)) {
-        const float mn = fmaxf(m, tmax);
-        const float mref = mn == -INFINITY ? 0.f : mn;
-        const float alpha = exp2f(m - mref);
-        l *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
-        m = mn;
-      }
-      const float mref = m == -INFINITY ? 0.f : m;
-      float rs = 0.f;
-#pragma unroll
-      for (int st = 0; st < 4; ++st)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const float e = exp2f(sc[st][i] - mref); sc[st][i] = e; rs += e; }
-      rs = xor16_sum(rs);
-      rs = xor32_sum(rs);
-      l += rs;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8_t pf = pack_p(sc[2 * ks], sc[2 * ks + 1]);
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt)
-          o[dt] = mfma16(as_bf16x8(*reinterpret_cast<const uint4*>(vb + v_lds_off(ks, 16 * dt + col, g))), pf, o[dt]);
-      }
-    }
-    if (more) lwrite(cur ^ 1);
-    __syncthreads();
-  }
-
-  if (my_row < q_len) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-    uint16_t* orow = out + ((size_t)(q_begin + my_row) * Hq + hq) * D;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      uint2 pk;
-      pk.x = pack2bf(o[dt][0] * inv, o[dt][1] * inv);
-      pk.y = pack2bf(o[dt][2] * inv, o[dt][3] * inv);
-      *reinterpret_cast<uint2*>(orow + 16 * dt + 4 * g) = pk;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// Prefill v4: 4 waves x 32 query rows on v_mfma_f32_32x32x16_bf16 (128-row tiles, as v3).
-//   * S^T = K . Q^T per 32-key half-tile: A = K rows from LDS, B = Q^T from registers (8 k-steps
-//     over D = 128).  C/D of 32x32: col = lane & 31 (query), row = 8(i>>2) + 4(lane>>5) + (i&3)
-//     (key), so each lane owns one query row's scores for 16 of every 32 keys (the other 16 in
-//     lane ^ 32): row max / sum = 31 local ops + one xor-32 shuffle.
-//   * O^T = V^T . P^T: the S^T accumulator IS the P^T B-operand (guide §3: k-step s of a 32-key
-//     tile = registers 8s..8s+7, key order 16s + 8(j>>2) + 4h + (j&3)); the V^T LDS image stores
-//     each d row's 64 keys in exactly that slot order, so the A fragment is one ds_read_b128.
-//     The cache's V^T blocks are in the decode (16x16) slot order; the permutation to the 32x32
-//     order is applied while writing the LDS image (two 8-byte stores per 16-byte load).
-//   * K / V^T tiles (64 keys) double-buffered in LDS, register-staged (loads for tile t+1 issued
-//     before tile t's MFMAs, LDS writes after), one barrier per tile; deferred rescale as in v3.
-//   * vs v3 (16x16x32, 16 rows/wave): every LDS fragment byte now feeds twice the FLOPs.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ f32x16_t mfma32(bf16x8_t a, bf16x8_t b, f32x16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// V^T image: row d (64 keys = 128 B), 16-byte chunk c at d*128 + ((c ^ (d & 7)) << 4)
-__device__ __forceinline__ int v4_off(int d, int c) { return d * 128 + ((c ^ (d & 7)) << 4); }
-
-template <int MINW>
-__global__ void __launch_bounds__(256, MINW) prefill_paged_kernel_v4(
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
-    const int32_t* __restrict__ block_tables, const int32_t* __restrict__ cu_q, const int32_t* __restrict__ ctx_lens,
-    const int32_t* __restrict__ tile_seq, const int32_t* __restrict__ tile_q0, float scale_log2, int Hq, int Hkv,
-    int max_blocks, uint16_t* __restrict__ out) {
-  constexpr int D = 128;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // LDS: [K buf0 16K][K buf1 16K][V buf0 16K][V buf1 16K]
-  const int t = blockIdx.x, hq = blockIdx.y;
-  const int G = Hq / Hkv, hk = hq / G;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tid = threadIdx.x;
-  const int l32 = lane & 31, hi = lane >> 5;
-  const int s = tile_seq[t], qs = tile_q0[t];
-  const int q_begin = cu_q[s], q_len = cu_q[s + 1] - q_begin;
-  const int ctx = ctx_lens[s];
-  const int pos_base = ctx - q_len;
-  const int row_last = min(qs + PF_ROWS - 1, q_len - 1);
-  const int kend = pos_base + row_last + 1;
-  const int ntiles = (kend + PF_KT - 1) / PF_KT;
-  const int32_t* bt = block_tables + (size_t)s * max_blocks;
-
-  const int my_row = qs + 32 * w + l32;
-  const int my_pos = pos_base + my_row;
-  const int wave_min_pos = pos_base + qs + 32 * w;
-  // Q^T B-operand, pre-scaled into the exp2 domain: k-step ks holds Q[row][16ks + 8hi .. +7]
-  bf16x8_t qf[8];
-  {
-    const int rr = min(my_row, q_len - 1);
-    const uint16_t* qr = q + ((size_t)(q_begin + rr) * Hq + hq) * D;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      float f[8];
-      unpack8(*reinterpret_cast<const uint4*>(qr + 16 * ks + 8 * hi), f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] *= scale_log2;
-      qf[ks] = as_bf16x8(pack8(f));
-    }
-  }
-
-  // staging: 1024 16-B pieces of K + 1024 of V per tile, 4 + 4 per thread
-  uint4 kst[4], vst[4];
-  auto gload = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int id = tid + 256 * i;
-      {  // K: row = id >> 4 (key in tile), chunk = id & 15
-        const int row = id >> 4, ch = id & 15, key = kt * PF_KT + row;
-        kst[i] = key < kend ? *reinterpret_cast<const uint4*>(
-                                  kc + (((size_t)bt[key / KV_BS] * Hkv + hk) * KV_BS + (key % KV_BS)) * D + ch * 8)
-                            : make_uint4(0, 0, 0, 0);
-      }
-      {  // V^T: block bi = id >> 9, d = (id >> 2) & 127, cache chunk g = id & 3 (slots 8g..8g+7)
-        const int bi = id >> 9, d = (id >> 2) & 127, g = id & 3;
-        const int key0 = kt * PF_KT + bi * KV_BS;
-        vst[i] = key0 < kend ? *reinterpret_cast<const uint4*>(
-                                   vc + ((size_t)bt[key0 / KV_BS] * Hkv + hk) * D * KV_BS + kv_v_off(d, 8 * g, D))
-                             : make_uint4(0, 0, 0, 0);
-      }
-    }
-  };
-  auto lwrite = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int id = tid + 256 * i;
-      *reinterpret_cast<uint4*>(smem + buf * 16384 + k_lds_off(id >> 4, id & 15)) = kst[i];
-      // cache slots 8g..8g+3 hold keys 4g..4g+3 and 8g+4..8g+7 hold keys 16+4g..16+4g+3; in the
-      // 32x32 order key k of a 32-block sits at slot 16(k>>4) + 8((k>>2)&1) + 4((k&15)>>3) + (k&3)
-      const int bi = id >> 9, d = (id >> 2) & 127, g = id & 3;
-      const int base = 32 * bi + 8 * (g & 1) + 4 * (g >> 1);        // slot of key 4g (s = 0)
-      char* vrow = smem + 32768 + buf * 16384;
-      const uint2 lo = make_uint2(vst[i].x, vst[i].y), hi2 = make_uint2(vst[i].z, vst[i].w);
-      *reinterpret_cast<uint2*>(vrow + v4_off(d, base >> 3) + (base & 7) * 2) = lo;
-      *reinterpret_cast<uint2*>(vrow + v4_off(d, (base + 16) >> 3) + ((base + 16) & 7) * 2) = hi2;
-    }
-  };
-
-  f32x16_t o[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-  float m = -INFINITY, l = 0.f;
-
-  gload(0);
-  lwrite(0);
-  __syncthreads();
-  for (int kt = 0; kt < ntiles; ++kt) {
-    const int cur = kt & 1;
-    const bool more = kt + 1 < ntiles;
-    if (more) gload(kt + 1);
-
-    const char* kb = smem + cur * 16384;
-    const char* vb = smem + 32768 + cur * 16384;
-    const int key0 = kt * PF_KT;
-    if (key0 <= wave_min_pos + 31) {
-      f32x16_t sc[2];
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[hf][r] = 0.f;
-        const int row = 32 * hf + l32;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
-          sc[hf] = mfma32(as_bf16x8(*reinterpret_cast<const uint4*>(kb + k_lds_off(row, 2 * ks + hi))), qf[ks], sc[hf]);
-      }
-      if (key0 + PF_KT - 1 > wave_min_pos) {  // diagonal tile: causal mask
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            if (key0 + 32 * hf + 8 * (r >> 2) + 4 * hi + (r & 3) > my_pos) sc[hf][r] = -INFINITY;
-      }
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, sc[hf][r]);
-      tmax = xor32_max(tmax);
-      if (!__all(tmax - m <= RESCALE_THR)) {
-        const float mn = fmaxf(m, tmax);
-        const float mref = mn == -INFINITY ? 0.f : mn;
-        const float alpha = exp2f(m - mref);
-        l *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
-        m = mn;
-      }
-      const float mref = m == -INFINITY ? 0.f : m;
-      float rs = 0.f;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { const float e = exp2f(sc[hf][r] - mref); sc[hf][r] = e; rs += e; }
-      rs = xor32_sum(rs);
-      l += rs;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-        for (int ss = 0; ss < 2; ++ss) {
-          uint4 u;
-          u.x = pack2bf(sc[hf][8 * ss + 0], sc[hf][8 * ss + 1]);
-          u.y = pack2bf(sc[hf][8 * ss + 2], sc[hf][8 * ss + 3]);
-          u.z = pack2bf(sc[hf][8 * ss + 4], sc[hf][8 * ss + 5]);
-          u.w = pack2bf(sc[hf][8 * ss + 6], sc[hf][8 * ss + 7]);
-          const bf16x8_t pf = as_bf16x8(u);
-          const int c = 4 * hf + 2 * ss + hi;     // V^T chunk of slots 32hf + 16ss + 8hi .. +7
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt)
-            o[dt] = mfma32(as_bf16x8(*reinterpret_cast<const uint4*>(vb + v4_off(32 * dt + l32, c))), pf, o[dt]);
-        }
-    }
-    if (more) lwrite(cur ^ 1);
-    __syncthreads();
-  }
-
-  if (my_row < q_len) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-    uint16_t* orow = out + ((size_t)(q_begin + my_row) * Hq + hq) * D;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {   // registers 4rg..4rg+3 = d 32dt + 8rg + 4hi + 0..3
-        uint2 pk;
-        pk.x = pack2bf(o[dt][4 * rg] * inv, o[dt][4 * rg + 1] * inv);
-        pk.y = pack2bf(o[dt][4 * rg + 2] * inv, o[dt][4 * rg + 3] * inv);
-        *reinterpret_cast<uint2*>(orow + 32 * dt + 8 * rg + 4 * hi) = pk;
-      }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// Prefill v5 (default): GQA-packed 8-wave tiles on v_mfma_f32_32x32x16_bf16.
+// Varlen causal prefill over the paged cache (D = 128, G = Hq / Hkv in {1, 2, 4, 8}): GQA-packed
+// 8-wave tiles on v_mfma_f32_32x32x16_bf16.
 // grid = (n_tiles, Hkv); block = 512 = 8 waves, 2 per SIMD.  A tile is QR = 256 / G query rows of
 // ONE sequence for ALL G query heads of kv-head hk: wave w takes head hk*G + (w % G) and rows
 // 32 (w / G) .. +31.  Every K/V byte staged in LDS therefore feeds 256 query rows (8 waves), and
 // the tile spans only 256/G positions, so at G = 4 the causal diagonal idles 4x fewer rows than a
-// 256-row single-head tile would.
+// 256-row single-head tile would.  Tile t covers query rows [tile_q0[t], +QR) of sequence
+// tile_seq[t]; those rows sit at positions ctx - q_len + row (chunked prefill / prefix reuse: keys
+// come from the cache).  The host orders tiles heaviest-first (most keys) so the causal triangle
+// drains evenly; the causal mask is applied only on tiles that cross the diagonal.
 //   * LDS per KV tile (64 keys): K 64 x 256 B (16-B chunk c of key r at r*256 + ((c ^ (r&15))<<4))
 //     and V^T 128 d-rows x 128 B copied AS STORED in the cache (decode slot order).  The decode
 //     order already fits the 32x32 PV: cache chunk g of a 32-key block holds keys {4g..4g+3,
@@ -859,11 +465,31 @@ __global__ void __launch_bounds__(256, MINW) prefill_paged_kernel_v4(
 //     one in-lane pack, no permutation anywhere.  V swizzle c ^ ((d>>1)&7) ^ ((d&1)<<2): the
 //     ds_read_b128 lane groups and the 8-lane ds_write_b128 groups are both conflict-free.
 //   * register-staged double buffer, one barrier per tile (loads for tile t+1 issued before tile
-//     t's MFMAs, LDS writes after); Q pre-scaled into the exp2 domain; deferred rescale
-//     (RESCALE_THR); row max / sum across the two half-waves with v_permlane32_swap (no LDS
+//     t's MFMAs, LDS writes after); Q pre-scaled into the exp2 domain; O rescaled only when the
+//     running max grows by > RESCALE_THR (guide T13; P is then bounded by 2^THR, exact after the
+//     final 1/l); row max / sum across the two half-waves with v_permlane32_swap (no LDS
 //     bpermute); per-lane partial row sums combined once at the end; v_exp_f32 / v_cvt_pk_bf16_f32
 //     directly; waves 4-7 at static priority 1 (the younger half loses VALU arbitration otherwise).
 // ------------------------------------------------------------------------------------------
+constexpr int PF_KT = 64;     // keys per tile
+#ifndef CFC_PF_QK_PIPE
+#define CFC_PF_QK_PIPE 1
+#endif
+constexpr int PF_QK_PIPE = CFC_PF_QK_PIPE;   // K fragments of a half-tile (2: of both) read ahead of its MFMAs
+#ifndef CFC_PF_V_EARLY
+#define CFC_PF_V_EARLY 1
+#endif
+// V fragments of the first PF_V_EARLY half-tiles read before the softmax (2: 251 VGPRs, 1 % slower,
+// profiles/r05_ab_prefill_attn_vearly2_rejected.log)
+constexpr int PF_V_EARLY = CFC_PF_V_EARLY;
+constexpr float RESCALE_THR = 8.0f;
+
+__device__ __forceinline__ int k_lds_off(int row, int ch) { return row * 256 + ((ch ^ (row & 15)) << 4); }
+
+__device__ __forceinline__ f32x16_t mfma32(bf16x8_t a, bf16x8_t b, f32x16_t c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
@@ -889,7 +515,7 @@ __device__ __forceinline__ float quad_sum(float x) {
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return pair_sum(__uint_as_float(r[0]) + __uint_as_float(r[1]));
 }
-__device__ __forceinline__ int v5_off(int d, int c) { return d * 128 + ((c ^ ((d >> 1) & 7) ^ ((d & 1) << 2)) << 4); }
+__device__ __forceinline__ int v_lds_off(int d, int c) { return d * 128 + ((c ^ ((d >> 1) & 7) ^ ((d & 1) << 2)) << 4); }
 
 template <int G, bool F8 = false>
 __global__ void __launch_bounds__(512, 2) prefill_gqa_kernel(
@@ -987,14 +613,14 @@ __global__ void __launch_bounds__(512, 2) prefill_gqa_kernel(
       const int d = 2 * (e & 63), c = 4 * b + (e >> 6);
       const bool z = b ? z1 : z0;
       const uint4 zero = make_uint4(0, 0, 0, 0);
-      *reinterpret_cast<uint4*>(vb + v5_off(d, c)) = z ? zero : fp8x8_to_bf16x8(make_uint2(vs0.x, vs0.y));
-      *reinterpret_cast<uint4*>(vb + v5_off(d + 1, c)) = z ? zero : fp8x8_to_bf16x8(make_uint2(vs0.z, vs0.w));
+      *reinterpret_cast<uint4*>(vb + v_lds_off(d, c)) = z ? zero : fp8x8_to_bf16x8(make_uint2(vs0.x, vs0.y));
+      *reinterpret_cast<uint4*>(vb + v_lds_off(d + 1, c)) = z ? zero : fp8x8_to_bf16x8(make_uint2(vs0.z, vs0.w));
     } else {
       *reinterpret_cast<uint4*>(kb + k_lds_off(tid >> 4, tid & 15)) = ks0;
       *reinterpret_cast<uint4*>(kb + k_lds_off((tid >> 4) + 32, tid & 15)) = ks1;
       // element 8 tid of the [4][D][8] tile = slot chunk tid >> 7 of row tid & 127
-      *reinterpret_cast<uint4*>(vb + v5_off(tid & 127, tid >> 7)) = z0 ? make_uint4(0, 0, 0, 0) : vs0;
-      *reinterpret_cast<uint4*>(vb + v5_off(tid & 127, 4 + (tid >> 7))) = z1 ? make_uint4(0, 0, 0, 0) : vs1;
+      *reinterpret_cast<uint4*>(vb + v_lds_off(tid & 127, tid >> 7)) = z0 ? make_uint4(0, 0, 0, 0) : vs0;
+      *reinterpret_cast<uint4*>(vb + v_lds_off(tid & 127, 4 + (tid >> 7))) = z1 ? make_uint4(0, 0, 0, 0) : vs1;
     }
   };
 
@@ -1075,7 +701,7 @@ __global__ void __launch_bounds__(512, 2) prefill_gqa_kernel(
           for (int ss = 0; ss < 2; ++ss)
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
-              vf0[hf][ss][dt] = *reinterpret_cast<const uint4*>(vb + v5_off(32 * dt + l32, 4 * hf + 2 * ss + hi));
+              vf0[hf][ss][dt] = *reinterpret_cast<const uint4*>(vb + v_lds_off(32 * dt + l32, 4 * hf + 2 * ss + hi));
       }
       if (key0 + PF_KT - 1 > wave_min_pos) {  // diagonal tile: causal mask
 #pragma unroll
@@ -1138,7 +764,7 @@ __global__ void __launch_bounds__(512, 2) prefill_gqa_kernel(
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt)
             o[dt] = mfma32(as_bf16x8(hf < PF_V_EARLY ? vf0[hf][ss][dt]
-                                                     : *reinterpret_cast<const uint4*>(vb + v5_off(32 * dt + l32, c))),
+                                                     : *reinterpret_cast<const uint4*>(vb + v_lds_off(32 * dt + l32, c))),
                            pf, o[dt]);
         }
     }
@@ -1413,15 +1039,6 @@ CFC_API int cfc_paged_decode_attention(const void* q, const void* k_cache, const
                                     shared_blocks);
 }
 
-// Timing ablations of the fused decode RoPE (scripts/probe_decode_rope_fused.py): bit 1 skips the new
-// key's cache row, bit 2 the V^T slot-group store, bit 4 makes that store nontemporal.  Results are wrong
-// with bits 1 / 2 set; production never sets it.
-static int g_dec_rope_probe = 0;
-CFC_API int cfc_set_decode_rope_probe(int bits) {
-  g_dec_rope_probe = bits;
-  return 0;
-}
-
 // Decode attention with the step's RoPE + KV write in its prologue (DecRope).  qkv [B, (Hq+2Hkv)*128]
 // bf16 OR part [split, B, (Hq+2Hkv)*128] fp32 slabs (exactly one non-null); positions / slots [B];
 // fp8 != 0: e4m3 caches (K / k_scale, V / v_scale).  Writes out [B, Hq, 128]; q never leaves the chip.
@@ -1432,8 +1049,7 @@ CFC_API int cfc_paged_decode_rope_attention(const void* qkv, const float* part, 
                                             int window, int fp8, float k_scale, float v_scale, float* part_o,
                                             float* part_ml, void* out, const int32_t* shared_blocks,
                                             hipStream_t stream) {
-  const DecRope rp{(const uint16_t*)qkv, part, split, positions, slots, cos_sin, 1.f / k_scale, 1.f / v_scale,
-                   g_dec_rope_probe};
+  const DecRope rp{(const uint16_t*)qkv, part, split, positions, slots, cos_sin, 1.f / k_scale, 1.f / v_scale};
   if (fp8)
     return launch_paged_decode<true>(nullptr, k_cache, v_cache, block_tables, ctx_lens, B, Hq, Hkv, head_dim,
                                      max_blocks, part_blocks, P, scale * k_scale, window, v_scale, part_o, part_ml,
@@ -1454,85 +1070,60 @@ CFC_API int cfc_paged_decode_attention_fp8(const void* q, const void* k_cache, c
                                    nullptr, shared_blocks);
 }
 
-CFC_API int cfc_prefill_tile_rows() { return PF_ROWS; }
-
-static int prefill_variant() {
-  static const int v = [] { const char* e = getenv("CFC_PREFILL_VARIANT"); return e ? atoi(e) : 5; }();
-  return v;
-}
 static int prefill_xcd_local() {
   static const int v = [] { const char* e = getenv("CFC_PREFILL_XCD"); return e ? atoi(e) : 1; }();
   return v;
 }
 
-// Query rows per tile the default prefill kernel expects for Hq / Hkv heads (the host tiler's
-// granularity): 256 / G on the GQA-packed kernel, else PF_ROWS.
+// Query rows per tile the prefill kernel expects for Hq / Hkv heads (the host tiler's granularity):
+// 256 / G for G = Hq / Hkv in {1, 2, 4, 8}; 0: no prefill kernel for this head ratio.
 CFC_API int cfc_prefill_rows(int Hq, int Hkv) {
-  if (Hkv <= 0 || Hq % Hkv) return PF_ROWS;
+  if (Hkv <= 0 || Hq % Hkv) return 0;
   const int G = Hq / Hkv;
-  const bool v5 = prefill_variant() == 5 && (G == 1 || G == 2 || G == 4 || G == 8);
-  return v5 ? 256 / G : PF_ROWS;
+  return (G == 1 || G == 2 || G == 4 || G == 8) ? 256 / G : 0;
+}
+
+// F8: e4m3 caches; the caller folds k_scale into scale, v_scale multiplies the output.
+template <bool F8>
+static int launch_prefill(const void* q, const void* k_cache, const void* v_cache, const int32_t* block_tables,
+                          const int32_t* cu_q, const int32_t* ctx_lens, const int32_t* tile_seq,
+                          const int32_t* tile_q0, int n_tiles, int tile_rows, int Hq, int Hkv, int head_dim,
+                          int max_blocks, float scale, int window, float v_scale, void* out, hipStream_t stream) {
+  if (head_dim != 128 || Hkv <= 0 || Hq % Hkv != 0 || window < 0) return -1;
+  const int rows = cfc_prefill_rows(Hq, Hkv);
+  if (rows == 0) return -3;                  // head ratio without a kernel
+  if (tile_rows != rows) return -2;          // tiles cut for another kernel
+  if (n_tiles <= 0) return 0;
+  const dim3 grid(n_tiles, Hkv);
+#define PF_CASE(GG) \
+  case GG: \
+    prefill_gqa_kernel<GG, F8><<<grid, 512, 65536, stream>>>( \
+        (const uint16_t*)q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tile_seq, tile_q0, scale * LOG2E, Hq, \
+        Hkv, max_blocks, window, v_scale, prefill_xcd_local(), (uint16_t*)out); \
+    break;
+  switch (Hq / Hkv) {
+    PF_CASE(1) PF_CASE(2) PF_CASE(4) PF_CASE(8)      // no other ratio has rows != 0
+  }
+#undef PF_CASE
+  return CFC_CHECK_LAUNCH();
 }
 
 CFC_API int cfc_prefill_attention(const void* q, const void* k_cache, const void* v_cache, const int32_t* block_tables,
                                   const int32_t* cu_q, const int32_t* ctx_lens, const int32_t* tile_seq,
                                   const int32_t* tile_q0, int n_tiles, int tile_rows, int Hq, int Hkv, int head_dim,
                                   int max_blocks, float scale, int window, void* out, hipStream_t stream) {
-  if (head_dim != 128 || Hkv <= 0 || Hq % Hkv != 0 || window < 0) return -1;
-  if (tile_rows != cfc_prefill_rows(Hq, Hkv)) return -2;     // tiles cut for another kernel
-  if (n_tiles <= 0) return 0;
-  const size_t lds = 65536;
-  const int G = Hq / Hkv;
-#define PF_ARGS (const uint16_t*)q, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables, cu_q, ctx_lens, \
-    tile_seq, tile_q0, scale * LOG2E, Hq, Hkv, max_blocks, (uint16_t*)out
-#define PF5_ARGS (const uint16_t*)q, k_cache, v_cache, block_tables, cu_q, ctx_lens, \
-    tile_seq, tile_q0, scale * LOG2E, Hq, Hkv, max_blocks, window, 1.f, prefill_xcd_local(), (uint16_t*)out
-  if (tile_rows != PF_ROWS || (G * tile_rows == 256 && prefill_variant() == 5)) {
-    // 5: GQA-packed 8-wave kernel (default)
-    const dim3 grid(n_tiles, Hkv);
-    switch (G) {
-      case 1: prefill_gqa_kernel<1><<<grid, 512, lds, stream>>>(PF5_ARGS); break;
-      case 2: prefill_gqa_kernel<2><<<grid, 512, lds, stream>>>(PF5_ARGS); break;
-      case 4: prefill_gqa_kernel<4><<<grid, 512, lds, stream>>>(PF5_ARGS); break;
-      case 8: prefill_gqa_kernel<8><<<grid, 512, lds, stream>>>(PF5_ARGS); break;
-      default: return -3;
-    }
-    return CFC_CHECK_LAUNCH();
-  }
-  if (window > 0) return -4;     // sliding window: GQA-packed kernel only
-  // legacy single-head 128-row kernels: 0 = v3 <=128 VGPRs (2 workgroups / CU); 1 = v3 <=256 VGPRs;
-  // 2/3 = v4 (32x32 MFMA, 2 / 1 WG per CU)
-  const int variant = prefill_variant();
-  if (variant == 1) prefill_paged_kernel<2><<<dim3(n_tiles, Hq), 512, lds, stream>>>(PF_ARGS);
-  else if (variant == 2) prefill_paged_kernel_v4<2><<<dim3(n_tiles, Hq), 256, lds, stream>>>(PF_ARGS);
-  else if (variant == 3) prefill_paged_kernel_v4<1><<<dim3(n_tiles, Hq), 256, lds, stream>>>(PF_ARGS);
-  else prefill_paged_kernel<4><<<dim3(n_tiles, Hq), 512, lds, stream>>>(PF_ARGS);
-#undef PF_ARGS
-#undef PF5_ARGS
-  return CFC_CHECK_LAUNCH();
+  return launch_prefill<false>(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tile_seq, tile_q0, n_tiles,
+                               tile_rows, Hq, Hkv, head_dim, max_blocks, scale, window, 1.f, out, stream);
 }
 
-// FP8 (e4m3fn) caches holding K / k_scale and V / v_scale; GQA-packed kernel only (G in 1,2,4,8)
+// FP8 (e4m3fn) caches holding K / k_scale and V / v_scale
 CFC_API int cfc_prefill_attention_fp8(const void* q, const void* k_cache, const void* v_cache,
                                       const int32_t* block_tables, const int32_t* cu_q, const int32_t* ctx_lens,
                                       const int32_t* tile_seq, const int32_t* tile_q0, int n_tiles, int tile_rows,
                                       int Hq, int Hkv, int head_dim, int max_blocks, float scale, int window,
                                       float k_scale, float v_scale, void* out, hipStream_t stream) {
-  if (head_dim != 128 || Hkv <= 0 || Hq % Hkv != 0 || window < 0) return -1;
-  const int G = Hq / Hkv;
-  if (!(G == 1 || G == 2 || G == 4 || G == 8) || tile_rows * G != 256) return -2;
-  if (n_tiles <= 0) return 0;
-  const dim3 grid(n_tiles, Hkv);
-#define PF8_ARGS (const uint16_t*)q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tile_seq, tile_q0, \
-    scale * k_scale * LOG2E, Hq, Hkv, max_blocks, window, v_scale, prefill_xcd_local(), (uint16_t*)out
-  switch (G) {
-    case 1: prefill_gqa_kernel<1, true><<<grid, 512, 65536, stream>>>(PF8_ARGS); break;
-    case 2: prefill_gqa_kernel<2, true><<<grid, 512, 65536, stream>>>(PF8_ARGS); break;
-    case 4: prefill_gqa_kernel<4, true><<<grid, 512, 65536, stream>>>(PF8_ARGS); break;
-    default: prefill_gqa_kernel<8, true><<<grid, 512, 65536, stream>>>(PF8_ARGS); break;
-  }
-#undef PF8_ARGS
-  return CFC_CHECK_LAUNCH();
+  return launch_prefill<true>(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tile_seq, tile_q0, n_tiles,
+                              tile_rows, Hq, Hkv, head_dim, max_blocks, scale * k_scale, window, v_scale, out, stream);
 }
 
 CFC_API int cfc_encoder_rows() { return ENC_ROWS; }

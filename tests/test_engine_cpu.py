@@ -317,6 +317,59 @@ def test_retired_gemv_norm_switch_fails_at_model_construction(monkeypatch):
     DecoderModel(DecoderWeights.random(cfg, "cpu", seed=0))
 
 
+def test_retired_prefill_attention_variant_switch_is_an_error(monkeypatch):
+    """CFC_PREFILL_VARIANT=0..3 selected prefill attention kernels that no longer exist: an error
+    that names the variable; unset, empty and 5 (the kernel that is left) ask for nothing else."""
+    from copilot_for_consensus_amd.ops import kernels as K
+    monkeypatch.delenv("CFC_PREFILL_VARIANT", raising=False)
+    rows = K.prefill_rows(8, 2)
+    assert rows > 0
+    for live in ("", "5"):
+        monkeypatch.setenv("CFC_PREFILL_VARIANT", live)
+        assert K.prefill_rows(8, 2) == rows
+    for gone in ("0", "1", "2", "3"):
+        monkeypatch.setenv("CFC_PREFILL_VARIANT", gone)
+        with pytest.raises(ValueError, match="CFC_PREFILL_VARIANT.*removed"):
+            K.prefill_rows(8, 2)
+
+
+def test_decode_workspace_numel_is_partial_outputs_plus_max_sum_pairs():
+    from copilot_for_consensus_amd.ops import kernels as K
+    for B, Hq, D, P in [(1, 32, 128, 2), (3, 8, 128, 7), (128, 32, 128, 64)]:
+        assert K.decode_workspace_numel(B, Hq, D, P) == B * Hq * P * (D + 2)
+
+
+@pytest.mark.parametrize("max_blocks", [8, 9])
+@pytest.mark.parametrize("part_blocks", [4, -1, -3])
+def test_decode_launch_plan_partitions_and_workspace_views(part_blocks, max_blocks):
+    """part_blocks > 0: fixed partitions of that many blocks, P = ceil(max_blocks / part_blocks);
+    -P: P balanced partitions (part_blocks 0 for the kernel).  P > 1 cuts the workspace into the
+    [B, Hq, P, D] partial outputs and the [B, Hq, P, 2] (max, sum) pairs behind them."""
+    import math
+
+    from copilot_for_consensus_amd.ops import kernels as K
+    B, Hq, D = 3, 8, 128
+    want_p = math.ceil(max_blocks / part_blocks) if part_blocks > 0 else -part_blocks
+    pb, P, part_o, part_ml = K._decode_plan(B, Hq, D, max_blocks, part_blocks, None, None, "cpu")
+    assert (pb, P) == (max(part_blocks, 0), want_p)
+    if P == 1:
+        assert part_o is None and part_ml is None
+    else:
+        assert part_o.dtype == torch.float32 and part_o.numel() == K.decode_workspace_numel(B, Hq, D, P)
+        assert part_ml.numel() == B * Hq * P * 2
+        assert part_ml.data_ptr() == part_o.data_ptr() + 4 * B * Hq * P * D
+        ws = torch.empty(part_o.numel() + 5)     # a caller's (larger) workspace is used as it is
+        assert K._decode_plan(B, Hq, D, max_blocks, part_blocks, None, ws, "cpu")[2] is ws
+
+
+def test_decode_launch_plan_balanced_partitioning_needs_a_count():
+    from copilot_for_consensus_amd.ops import kernels as K
+    with pytest.raises(ValueError, match="num_partitions"):
+        K._decode_plan(3, 8, 128, 8, 0, None, None, "cpu")
+    assert K._decode_plan(3, 8, 128, 8, 0, 1, None, "cpu")[:2] == (0, 1)
+    assert K._decode_plan(3, 8, 128, 8, 0, 5, None, "cpu")[:2] == (0, 5)
+
+
 def test_prefill_tile_order_groups_sequences_by_l2_budget_heaviest_first_inside():
     """The prefill attention's tile order (ops.kernels.prefill_tiles with ctx_lens): consecutive
     sequences in groups of at most PREFILL_GROUP_CTX context tokens, groups in order, each group's

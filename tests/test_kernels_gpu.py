@@ -212,6 +212,28 @@ def test_prefill_attention(G):
     _close(out, ref, 2e-2)
 
 
+@pytest.mark.parametrize("Hq", [6, 32])
+def test_prefill_attention_refuses_head_ratio_without_kernel(Hq):
+    """Hq / Hkv outside {1, 2, 4, 8} (here 3 and 16) has no prefill kernel: a ValueError before
+    anything is allocated or launched, ``out`` untouched.  Decode attention supports G = 16."""
+    Hkv, D = 2, 128
+    kc, vc, bt = _fill_cache([1], Hkv, D)
+    q = torch.randn(1, Hq, D).bfloat16()
+    cu_t, cl = torch.tensor([0, 1], dtype=torch.int32), torch.tensor([1], dtype=torch.int32)
+    dev = [t.to(DEV) for t in (q, kc, vc, bt, cu_t, cl)]
+    buf = torch.full((1, Hq, D), 7.0, device=DEV).bfloat16()
+    with pytest.raises(ValueError, match=rf"Hq={Hq}, Hkv={Hkv}.*1, 2, 4 or 8"):
+        K.prefill_attention(*dev, 1 / math.sqrt(D), out=buf)
+    torch.cuda.synchronize()
+    assert torch.equal(buf, torch.full_like(buf, 7.0))
+    with pytest.raises(ValueError):
+        K.prefill_rows(Hq, Hkv)
+    if Hq == 16 * Hkv:
+        ref = R.paged_decode_attention(q, kc, vc, bt, cl, 1 / math.sqrt(D))
+        out = K.paged_decode_attention(dev[0], dev[1], dev[2], dev[3], dev[5], 1 / math.sqrt(D))
+        _close(out, ref, 2e-2)
+
+
 @pytest.mark.parametrize("D", [32, 64])
 def test_encoder_attention(D):
     H = 4
