@@ -219,7 +219,15 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, o
     partitions of each sequence's own context (what the engine uses).  ``window`` > 0: sliding-window
     attention over the last ``window`` keys (Mistral v0.1).  ``shared_blocks`` (device int32 [1]):
     every sequence's first that-many blocks are read through the caches (the batch's shared prefix
-    blocks), the rest nontemporal."""
+    blocks), the rest nontemporal.
+
+    Stale-slot contract: the kernel reads whole 32-key blocks and multiplies the masked keys' weights
+    (exact zeros) into V as read, so every slot of every block a table row names up to
+    ``ceil(ctx / 32)`` must hold FINITE values, also the slots at and past ``ctx``; ``ctx_lens`` >= 1
+    and every table entry is a valid block.  The engine's pool is zero-initialised for this
+    (runtime/kv_cache.py) and the cache writers only store finite values.  Known limit: a block
+    left behind by a sequence that produced NaN / Inf breaks the contract for the block's next
+    owner (0 * NaN); the kernels are not hardened against that."""
     if not q.is_cuda:
         return ref.paged_decode_attention(q, k_cache, v_cache, block_tables, ctx_lens, scale, window=window,
                                           k_scale=k_scale, v_scale=v_scale)
@@ -343,7 +351,13 @@ def prefill_tiles(cu_q: list[int], tile: int = PREFILL_TILE_ROWS, ctx_lens: list
 def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, scale, tiles=None, out=None, window=0,
                       k_scale=1.0, v_scale=1.0):
     """q [T, Hq, D] (packed varlen); cu_q [S+1] int32; ctx_lens [S] int32 (cached + new);
-    ``window`` > 0: sliding-window attention.  Hq / Hkv must be 1, 2, 4 or 8 (:func:`prefill_rows`)."""
+    ``window`` > 0: sliding-window attention.  Hq / Hkv must be 1, 2, 4 or 8 (:func:`prefill_rows`).
+
+    Stale-slot contract, as for :func:`paged_decode_attention`: the kernel stages whole 64-key tiles
+    and multiplies masked weights (exact zeros) into V as read, so every slot of a sequence's blocks
+    up to ``ceil(ctx / 32)`` must hold finite values, ``ctx_lens`` >= 1 and the table entries are
+    valid blocks (a zero-initialised pool, finite writes).  Known limit: a block a NaN-producing
+    sequence left behind poisons its next owner; the kernel is not hardened against that."""
     if not q.is_cuda:
         return ref.prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, scale, window=window,
                                      k_scale=k_scale, v_scale=v_scale)
