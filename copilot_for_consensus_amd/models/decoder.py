@@ -139,6 +139,9 @@ class DecoderWeights:
         self.q_lm_head = None
         # opt-in W8A8 FP8 projections (e4m3fn + per-output-channel scales): to_fp8()
         self.fp8_layers: list[dict] | None = None
+        # second copies of the FP8 projections in the FP8 decode GEMM's fragment-packed layout
+        # (K.PackedWeightF8): pack_fp8_decode()
+        self.fp8_packed: list[dict] | None = None
         # second copies of the decode projections in the decode GEMM's fragment-packed layout
         # (K.PackedWeight): pack_decode()
         self.packed: list[dict] | None = None
@@ -434,6 +437,16 @@ class DecoderWeights:
             torch.cuda.empty_cache()
         return self
 
+    def pack_fp8_decode(self, m: int = 128) -> "DecoderWeights":
+        """Copy every FP8 projection into the FP8 decode GEMM's fragment-packed layout
+        (K.pack_f8dgemm_weight), tiled as K.f8dgemm_config picks for an m-row batch.  The row-major
+        FP8 copies stay -- the prefill still runs on K.linear_fp8 -- so this is a second FP8 copy of
+        the projections (about 7 GB on Mistral-7B)."""
+        if self.fp8_packed is None:
+            self.fp8_packed = [{k: K.pack_f8dgemm_weight(*q[k], m=m) for k in self.FP8_PROJECTIONS}
+                               for q in self.fp8_layers]
+        return self
+
     DECODE_PACKED = ("qkv", "o", "gate_up", "down")
 
     def packed_bytes(self) -> int:
@@ -488,6 +501,7 @@ class DecoderWeights:
         n += self.packed_lm_head.nbytes() if self.packed_lm_head is not None else 0
         for q in self.fp8_layers or []:
             n += sum(a.numel() * a.element_size() + b.numel() * b.element_size() for a, b in q.values())
+        n += sum(p.nbytes() for layer in self.fp8_packed or [] for p in layer.values())
         return n + sum(t.numel() * t.element_size() for t in (self.embed, self.final_norm, self.lm_head)
                        if t is not None)
 
@@ -577,6 +591,17 @@ class DecoderModel:
         if self.fp8:
             mode = "lib"          # W8A8: every projection through linear_fp8 (bf16 fused paths need bf16 weights)
         self.decode_gemm = mode
+        # W8A8 decode steps of up to K.F8DGEMM_MAX_M rows on the hand-written FP8 decode GEMM
+        # (csrc/kernels/f8dgemm.hip) through the one decode layer loop, over a fragment-packed second
+        # copy of the FP8 projections: CFC_DECODE_FP8_GEMM=1.  Off by default (unset / 0): the
+        # library loop above.  Larger batches, TP > 1 and the CPU keep the library loop either way
+        f8 = os.environ.get("CFC_DECODE_FP8_GEMM", "0")
+        if f8 not in ("0", "1"):
+            raise ValueError(f"CFC_DECODE_FP8_GEMM={f8!r}: expected 0 or 1")
+        self.decode_f8gemm = (f8 == "1" and self.fp8 and weights.device.type == "cuda" and weights.tp_size == 1
+                              and all(K.f8dgemm_ok(1, s) for s in weights.projection_shapes().values()))
+        if self.decode_f8gemm:
+            weights.pack_fp8_decode()
         # prefill GEMM (packed prompt rows): "hip" = the hand-written MFMA GEMM (csrc/kernels/pgemm.hip,
         # SwiGLU fused into gate/up, reading the packed weights), "lib" = the library GEMM + silu_mul
         # (CFC_PREFILL_GEMM); CFC_PGEMM_VARIANT picks pgemm's kernel, one of K.PGEMM_VARIANTS
@@ -973,10 +998,13 @@ class DecoderModel:
         quantized decode GEMM (B <= self.qgemm_max_m); "gemv" -- the bf16 weight-streaming
         GEMV; "dgemm" -- the hand-written bf16 decode GEMM; "splitk" -- library GEMMs with the
         split-K residual + RMSNorm reduce; "lib" -- plain library GEMMs (CPU, fp8, TP without dgemm);
+        "f8gemm" -- W8A8 weights on the hand-written FP8 decode GEMM (CFC_DECODE_FP8_GEMM=1, B <= 128);
         "scratch" -- quantized-blocks-only weights at a batch the quantized kernels do not take: the
         bf16 decode GEMM on the scratch each projection is unpacked into just before (where a model
         with bf16 copies would return "dgemm", "gemv" or "splitk")."""
         small = B <= K.GEMV_MAX_M
+        if self.decode_f8gemm and on_gpu and B <= K.F8DGEMM_MAX_M:
+            return "f8gemm"
         if self.w.quant_only:
             return "qgemv" if small else "qgemm" if B <= self.qgemm_max_m else "scratch"
         if on_gpu and self.decode_qgemm and K.GEMV_MAX_M < B <= self.qgemm_max_m:
@@ -1060,11 +1088,12 @@ class DecoderModel:
         ``_<family>_gate_up``) runs on the ``quant`` family ("qgemv", "qgemm" or None) where that
         takes the projection -- it returns None where it does not: no quantized copy, a shape or a
         type pairing its kernel refuses -- and otherwise on the ``base`` family ("dgemm", "gemv" or
-        "splitk") over the bf16 weights of the same layer."""
+        "splitk") over the bf16 weights of the same layer, or "f8gemm" over the W8A8 ones."""
         cfg, w = self.cfg, self.w
         B = x.shape[0]
         residual = x.clone()
-        h = K.rmsnorm(x, w.layers[0]["attn_norm"], cfg.rms_eps)
+        # the f8gemm family carries h as the quantised (x8, scale) pair its projections read
+        h = (K.rmsnorm_fp8 if base == "f8gemm" else K.rmsnorm)(x, w.layers[0]["attn_norm"], cfg.rms_eps)
 
         roles = {r: (getattr(self, f"_{quant}_{r}") if quant else None, getattr(self, f"_{base}_{r}"))
                  for r in ("qkv", "row", "gate_up")}
@@ -1183,6 +1212,27 @@ class DecoderModel:
         B, Kd = x.shape
         bn, split = K.dgemm_config(B, w.shape[0], Kd, bn=getattr(w, "bn", None))
         return self._tp_norm(K.dgemm(x, w, "part", split, bn=bn), residual, norm_w)
+
+    # -- FP8 decode GEMM (W8A8, B <= 128, f8dgemm.hip) over the packed FP8 copies.  h is the (x8, scale)
+    # pair: the reduces that end o and down quantise the next projection's input in the same launch
+    # (K.splitk_residual_rmsnorm_fp8), so a layer-step has the bf16 family's launch count plus the
+    # attention output's quantisation and silu_mul_fp8.  The rounding points are the library FP8 loop's
+
+    def _f8gemm_qkv(self, i, h):
+        wq = self.w.fp8_packed[i]["qkv"]
+        return K.f8dgemm(*h, wq, "part", self.qkv_split or K.f8dgemm_config(h[0].shape[0], wq.N, wq.K, wq.bn)[1])
+
+    def _f8gemm_row(self, i, name, x, residual, norm_w):
+        part = K.f8dgemm(*(x if isinstance(x, tuple) else K.quant_fp8_rows(x)), self.w.fp8_packed[i][name], "part")
+        if norm_w is self.w.final_norm:     # the last down: the step's bf16 hidden state
+            return K.splitk_residual_rmsnorm(part, residual, norm_w, self.cfg.rms_eps)
+        return K.splitk_residual_rmsnorm_fp8(part, residual, norm_w, self.cfg.rms_eps)
+
+    def _f8gemm_gate_up(self, i, h):
+        wg = self.w.fp8_packed[i]["gate_up"]
+        split = K.f8dgemm_config(h[0].shape[0], wg.N, wg.K, wg.bn)[1]
+        gu = K.f8dgemm(*h, wg, "bf16") if split == 1 else K.splitk_reduce(K.f8dgemm(*h, wg, "part", split))
+        return K.silu_mul_fp8(gu, interleaved=self.w.gate_up_interleaved)
 
     # -- bf16 GEMV (B <= 4, gemm.hip): gemv_tile_kernel over the packed copy when it is the only one
     # (qkv as k-slice slabs straight into the slab-reading RoPE / KV write), gemv_kernel over the

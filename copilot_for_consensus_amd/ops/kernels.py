@@ -1366,6 +1366,156 @@ def linear_fp8(x, w8: torch.Tensor, w_scale: torch.Tensor) -> torch.Tensor:
     return torch._scaled_mm(x8, w8.t(), scale_a=sx, scale_b=w_scale, out_dtype=torch.bfloat16)
 
 
+# ------------------------------------------------ W8A8 FP8 decode GEMM (f8dgemm.hip)
+
+F8DGEMM_MAX_M = 128                  # rows of X the FP8 decode GEMM takes (8 MFMA row tiles)
+F8DGEMM_BNS = (128, 112, 96, 64)     # W rows per workgroup the kernel is built for
+# dgemm_config's rates at one byte per element: NOT yet fitted for FP8 (the per-CU stream rates are
+# those of the bf16 kernel's loads, which this kernel issues unchanged)
+F8DGEMM_CU_RATE = DGEMM_CU_RATE
+F8DGEMM_X_RATE = DGEMM_X_RATE
+F8DGEMM_PART_RATE = DGEMM_PART_RATE
+
+
+class PackedWeightF8:
+    """An e4m3fn projection weight in the FP8 decode GEMM's fragment-packed layout for bn-row
+    workgroups (cfc_f8dgemm_pack: bytes [ceil(N/bn)][K/128][bn/16][2][64][16], rows past N zero) with
+    its per-output-channel scale [N] fp32.  Its own class, not a PackedWeight: the bf16 kernels
+    that read packed weights (dgemm, pgemm, gemv) refuse it by type."""
+
+    __slots__ = ("data", "scale", "N", "K", "bn")
+
+    def __init__(self, data: torch.Tensor, scale: torch.Tensor, N: int, K: int, bn: int):
+        self.data, self.scale, self.N, self.K, self.bn = data, scale, N, K, bn
+
+    @property
+    def shape(self):
+        return (self.N, self.K)
+
+    def nbytes(self) -> int:
+        return self.data.numel() + self.scale.numel() * 4
+
+
+def f8dgemm_ok(M: int, w) -> bool:
+    """Shapes the FP8 decode GEMM takes: 1 <= M <= 128, N % 64 == 0, K % 128 == 0 of a PackedWeightF8
+    (an (N, K) pair asks about the shape alone)."""
+    N, Kd = w.shape if isinstance(w, PackedWeightF8) else w
+    return 1 <= M <= F8DGEMM_MAX_M and N > 0 and N % 64 == 0 and Kd > 0 and Kd % 128 == 0
+
+
+@functools.lru_cache(maxsize=None)
+def f8dgemm_config(M: int, N: int, K: int, bn: int | None = None) -> tuple[int, int]:
+    """(W rows per workgroup, split-K) for one FP8 decode projection: dgemm_config's cost model at
+    one byte per element -- ceil(workgroups / CUs) rounds of a workgroup streaming its W slice and
+    re-reading its rows of X from L2, plus the fp32 slabs written and read back once.  K parts are
+    whole 128-k blocks; N need not be a multiple of bn (the last workgroup is padded)."""
+    bm = 16 if M <= 16 else 32 if M <= 32 else 64 if M <= 64 else 128
+    best = None
+    for cand in (bn,) if bn else F8DGEMM_BNS:
+        tiles = -(-N // cand)
+        for split in range(1, K // 128 + 1):
+            rounds = -(-tiles * split // DGEMM_CUS)
+            blk = -(-(K // 128) // split) * 128            # k of the longest part
+            t = rounds * (cand * blk / F8DGEMM_CU_RATE + bm * blk / F8DGEMM_X_RATE)
+            if split > 1:
+                t += 2 * split * M * N * 4 / F8DGEMM_PART_RATE
+            if best is None or t < best[0] - 1e-12:
+                best = (t, cand, split)
+    return best[1], best[2]
+
+
+def pack_f8dgemm_weight(w8: torch.Tensor, scale: torch.Tensor, bn: int | None = None, m: int = 128) -> PackedWeightF8:
+    """Row-major e4m3fn W[N, K] + its scale [1, N] (quant_fp8_weight) -> PackedWeightF8 for bn-row
+    workgroups (default: the tile width f8dgemm_config picks for an m-row batch)."""
+    N, Kd = w8.shape
+    if w8.dtype != torch.float8_e4m3fn or not f8dgemm_ok(1, (N, Kd)) or scale.numel() != N:
+        raise ValueError(f"pack_f8dgemm_weight: w {tuple(w8.shape)} {w8.dtype}, scale {tuple(scale.shape)} "
+                         "(e4m3fn, N % 64 == 0, K % 128 == 0)")
+    bn = bn or f8dgemm_config(m, N, Kd)[0]
+    if bn not in F8DGEMM_BNS:
+        raise ValueError(f"pack_f8dgemm_weight: bn {bn} not in {F8DGEMM_BNS}")
+    sc = scale.reshape(N).float().contiguous()
+    if w8.is_cuda:
+        w8 = w8.contiguous()
+        out = torch.empty(-(-N // bn) * bn * Kd, dtype=torch.uint8, device=w8.device)
+        check(kernels().cfc_f8dgemm_pack(w8.data_ptr(), out.data_ptr(), N, Kd, bn, _stream(w8)), "cfc_f8dgemm_pack")
+    else:
+        out = ref.pack_f8dgemm_weight(w8, bn).reshape(-1)
+    return PackedWeightF8(out, sc, N, Kd, bn)
+
+
+def _rowmajor_f8(w: PackedWeightF8) -> torch.Tensor:
+    return ref.unpack_f8dgemm_weight(w.data.view(-1, w.K // 128, w.bn // 16, 2, 64, 16), w.N)
+
+
+def f8dgemm(x8: torch.Tensor, sx: torch.Tensor, w: PackedWeightF8, epi: str = "part", split: int | None = None,
+            out: torch.Tensor | None = None, part: torch.Tensor | None = None) -> torch.Tensor:
+    """One launch of the FP8 decode GEMM: (x8 [M <= 128, K] e4m3fn, sx [M, 1] fp32) @ w^T with both
+    scales applied.  ``epi`` "part": fp32 split-K slabs ``part`` [split, M, N] (default: the split-K
+    workspace; ``split`` default: the cost model's); "bf16" (split 1): ``out`` [M, N].  ``part`` /
+    ``out`` may be column ranges of wider buffers (unit column stride, 16- / 8-byte aligned rows)."""
+    if not isinstance(w, PackedWeightF8) or x8.dim() != 2 or x8.dtype != torch.float8_e4m3fn:
+        raise ValueError("f8dgemm: x8 must be e4m3fn [M, K] and w a PackedWeightF8")
+    M, Kd = x8.shape
+    N = w.N
+    if Kd != w.K or not f8dgemm_ok(M, w) or sx.numel() != M or sx.dtype != torch.float32:
+        raise ValueError(f"f8dgemm: x8 {tuple(x8.shape)}, sx {tuple(sx.shape)} {sx.dtype} vs weight [{w.N}, {w.K}] "
+                         f"(M <= {F8DGEMM_MAX_M}, N % 64 == 0, K % 128 == 0)")
+    if epi not in ("part", "bf16"):
+        raise ValueError(f"f8dgemm: epi {epi!r}: expected part or bf16")
+    if epi == "bf16":
+        if split not in (None, 1):
+            raise ValueError("f8dgemm: the bf16 epilogue needs split 1")
+        split = 1
+    elif split is None:
+        split = part.shape[0] if part is not None else f8dgemm_config(M, N, Kd, w.bn)[1]
+    nb = Kd // 128
+    if not 1 <= split <= nb:
+        raise ValueError(f"f8dgemm: split {split} outside 1 .. K / 128 = {nb}")
+    dst = part if epi == "part" else out
+    if dst is None:
+        dst = (_workspace(x8.device, split * M * N)[:split * M * N].view(split, M, N) if epi == "part"
+               else torch.empty(M, N, dtype=torch.bfloat16, device=x8.device))
+    want = (split, M, N) if epi == "part" else (M, N)
+    if (tuple(dst.shape) != want or dst.dtype != (torch.float32 if epi == "part" else torch.bfloat16)
+            or dst.device != x8.device or dst.stride(-1) != 1):
+        raise ValueError(f"f8dgemm: output {tuple(dst.shape)} {dst.dtype}, expected {want}")
+    if not x8.is_cuda:
+        xd, wd = x8.float().double(), _rowmajor_f8(w).float().double()
+        sc = sx.reshape(M, 1).double() * w.scale.double()
+        for p in range(split):                 # the kernel's K parts: whole 128-k blocks
+            k0, k1 = p * nb // split * 128, (p + 1) * nb // split * 128
+            y = (xd[:, k0:k1] @ wd[:, k0:k1].t()) * sc
+            dst.copy_(y) if epi == "bf16" else dst[p].copy_(y)
+        return dst
+    ldo, slab = dst.stride(-2), (dst.stride(0) if epi == "part" else 0)
+    if not x8.is_contiguous() or not sx.is_contiguous():
+        raise ValueError("f8dgemm: x8 and sx must be contiguous")
+    check(kernels().cfc_f8dgemm(x8.data_ptr(), sx.data_ptr(), w.data.data_ptr(), w.scale.data_ptr(), M, N, Kd, split,
+                                0 if epi == "part" else 1, w.bn, dst.data_ptr() if epi == "part" else None,
+                                None if epi == "part" else dst.data_ptr(), int(slab), int(ldo), _stream(x8)),
+          "cfc_f8dgemm")
+    return dst
+
+
+def splitk_residual_rmsnorm_fp8(part: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor,
+                                eps: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """residual += bf16(sum of fp32 slabs [split, M, N]); returns quant_fp8_rows(RMSNorm(residual) *
+    norm_w) as (x8 [M, N] e4m3fn, scale [M, 1]) -- splitk_reduce -> rmsnorm_fp8(residual=...) in one
+    launch, bit-identical to the pair."""
+    split, M, N = part.shape
+    if not part.is_cuda:
+        return rmsnorm_fp8(part.sum(0).to(residual.dtype), norm_w, eps, residual=residual)
+    _req(part, torch.float32, "part")
+    _req(residual, torch.bfloat16, "residual")
+    out = torch.empty(M, N, dtype=torch.float8_e4m3fn, device=part.device)
+    scale = torch.empty(M, 1, dtype=torch.float32, device=part.device)
+    check(kernels().cfc_splitk_residual_rmsnorm_fp8(part.data_ptr(), split, M, N, residual.data_ptr(), norm_w.data_ptr(),
+                                                    float(eps), out.data_ptr(), scale.data_ptr(), _stream(part)),
+          "cfc_splitk_residual_rmsnorm_fp8")
+    return out, scale
+
+
 def bias_gelu(x, bias, out=None):
     if not x.is_cuda:
         return ref.bias_gelu(x, bias)

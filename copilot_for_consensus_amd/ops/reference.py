@@ -223,6 +223,25 @@ def unpack_dgemm_weight(p: torch.Tensor) -> torch.Tensor:
     return v.permute(0, 2, 4, 1, 3, 5).reshape(T * NW * 16, G * 32).contiguous()
 
 
+def pack_f8dgemm_weight(w8: torch.Tensor, bn: int) -> torch.Tensor:
+    """Row-major e4m3fn W[N, K] -> the FP8 decode GEMM's fragment-packed layout for bn-row workgroups,
+    bytes [ceil(N / bn), K / 128, bn / 16, 2, 64, 16]: packed[t, kb, w, h, 16 g + r, j] =
+    W[bn t + 16 w + r, 128 kb + 64 h + 16 g + j], rows past N zero (f8dgemm.hip)."""
+    N, K = w8.shape
+    T = -(-N // bn)
+    b = torch.zeros(T * bn, K, dtype=torch.uint8, device=w8.device)
+    b[:N] = w8.view(torch.uint8)
+    v = b.reshape(T, bn // 16, 16, K // 128, 2, 4, 16)             # t, w, r, kb, h, g, j
+    return v.permute(0, 3, 1, 4, 5, 2, 6).reshape(T, K // 128, bn // 16, 2, 64, 16).contiguous()
+
+
+def unpack_f8dgemm_weight(p: torch.Tensor, N: int) -> torch.Tensor:
+    """pack_f8dgemm_weight's inverse: the first N rows as row-major e4m3fn [N, K]."""
+    T, KB, NW = p.shape[0], p.shape[1], p.shape[2]
+    v = p.reshape(T, KB, NW, 2, 4, 16, 16)                         # t, kb, w, h, g, r, j
+    return v.permute(0, 2, 5, 1, 3, 4, 6).reshape(T * NW * 16, KB * 128)[:N].contiguous().view(torch.float8_e4m3fn)
+
+
 def silu_mul_interleaved(gu):
     F, G = gu.shape[-1] // 2, GU_GROUP
     v = gu.reshape(*gu.shape[:-1], F // G, 2, G).float()

@@ -13,11 +13,17 @@ namespace {
 // F8: out is e4m3fn of the bf16-rounded normalised row divided by a per-row scale
 // (scale[row] = amax / 448) -- the W8A8 projection's activation quantisation fused into the norm
 // that produces it, so the row makes no extra HBM round trip through a bf16 tensor.
-template <int VPT, bool F8>
+// PART: x is not a bf16 tensor but the bf16 rounding of the sum of `split` fp32 split-K slabs
+// (slab stride `slab` elements, summed p ascending from 0 as splitk_reduce_kernel does) -- the
+// decode GEMM's reduce, the residual add, the norm and the quantisation in one launch, every
+// operation in the order of splitk_reduce -> rmsnorm_fp8(residual), hence the same bits.
+template <int VPT, bool F8, bool PART = false>
 __global__ void __launch_bounds__(1024) rmsnorm_kernel(void* __restrict__ out, float* __restrict__ scale,
                                                       uint16_t* __restrict__ residual,
                                                       const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
-                                                      int dim, float eps, int add_residual) {
+                                                      int dim, float eps, int add_residual,
+                                                      const float* __restrict__ part = nullptr, int split = 0,
+                                                      size_t slab = 0) {
   __shared__ float red[16];
   const int row = blockIdx.x;
   const int nvec = dim >> 3;
@@ -29,7 +35,15 @@ __global__ void __launch_bounds__(1024) rmsnorm_kernel(void* __restrict__ out, f
   for (int i = 0; i < VPT; ++i) {
     const int c = threadIdx.x + i * blockDim.x;
     if (c < nvec) {
-      unpack8(xr[c], v[i]);
+      if constexpr (PART) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+        slab_sum8(part, split, slab, (size_t)row * dim + c * 8, a, b);
+        const float s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[i][j] = bf2f(f2bf(s[j]));
+      } else {
+        unpack8(xr[c], v[i]);
+      }
       if (add_residual) {
         float r[8];
         unpack8(rr[c], r);
@@ -195,6 +209,29 @@ CFC_API int cfc_rmsnorm_fp8(void* out, float* scale, void* residual, const void*
                             float eps, int add_residual, hipStream_t stream) {
   if (dim % 8 != 0 || rows <= 0) return -1;
   return launch_rmsnorm<true>(out, scale, residual, x, w, rows, dim, eps, add_residual, stream);
+}
+
+// cfc_splitk_reduce -> cfc_rmsnorm_fp8 with add_residual in one launch, bit-identical to the pair:
+// residual [M, N] += bf16(sum of the fp32 slabs part [split][M][N]); out [M, N] e4m3fn and scale [M]
+// are the per-row quantisation of bf16(RMSNorm(residual) * w).  N % 8 == 0, N <= 65536.
+CFC_API int cfc_splitk_residual_rmsnorm_fp8(const float* part, int split, int M, int N, void* residual, const void* w,
+                                            float eps, void* out, float* scale, hipStream_t stream) {
+  if (N <= 0 || N % 8 != 0 || M <= 0 || split < 1 || !part || !residual || !w || !out || !scale) return -1;
+  const int nvec = N / 8, block = pick_block(nvec);
+  const int vpt = (nvec + block - 1) / block;
+  auto r = (uint16_t*)residual;
+  auto wi = (const uint16_t*)w;
+  const size_t slab = (size_t)M * N;
+#define SRF_ARGS out, scale, r, nullptr, wi, N, eps, 1, part, split, slab
+  switch (vpt) {
+    case 1: rmsnorm_kernel<1, true, true><<<M, block, 0, stream>>>(SRF_ARGS); break;
+    case 2: rmsnorm_kernel<2, true, true><<<M, block, 0, stream>>>(SRF_ARGS); break;
+    case 3: case 4: rmsnorm_kernel<4, true, true><<<M, block, 0, stream>>>(SRF_ARGS); break;
+    case 5: case 6: case 7: case 8: rmsnorm_kernel<8, true, true><<<M, block, 0, stream>>>(SRF_ARGS); break;
+    default: return -2;
+  }
+#undef SRF_ARGS
+  return CFC_CHECK_LAUNCH();
 }
 
 CFC_API int cfc_layernorm(void* out, const void* x, const void* bias, const void* residual, const void* gamma,
