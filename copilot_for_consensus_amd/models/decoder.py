@@ -142,6 +142,7 @@ class DecoderWeights:
         # second copies of the FP8 projections in the FP8 decode GEMM's fragment-packed layout
         # (K.PackedWeightF8): pack_fp8_decode()
         self.fp8_packed: list[dict] | None = None
+        self.fp8_packed_only = False  # row-major FP8 projections freed after packing: drop_fp8_rowmajor()
         # second copies of the decode projections in the decode GEMM's fragment-packed layout
         # (K.PackedWeight): pack_decode()
         self.packed: list[dict] | None = None
@@ -439,12 +440,25 @@ class DecoderWeights:
 
     def pack_fp8_decode(self, m: int = 128) -> "DecoderWeights":
         """Copy every FP8 projection into the FP8 decode GEMM's fragment-packed layout
-        (K.pack_f8dgemm_weight), tiled as K.f8dgemm_config picks for an m-row batch.  The row-major
-        FP8 copies stay -- the prefill still runs on K.linear_fp8 -- so this is a second FP8 copy of
-        the projections (about 7 GB on Mistral-7B)."""
+        (K.pack_f8dgemm_weight), tiled as K.f8dgemm_config picks for an m-row batch.  The FP8
+        prefill GEMM (f8pgemm.hip) reads the same packed copy.  The row-major FP8 copies stay for
+        K.linear_fp8, so this is a second FP8 copy of the projections (about 7 GB on Mistral-7B)
+        until drop_fp8_rowmajor() frees them."""
         if self.fp8_packed is None:
             self.fp8_packed = [{k: K.pack_f8dgemm_weight(*q[k], m=m) for k in self.FP8_PROJECTIONS}
                                for q in self.fp8_layers]
+        return self
+
+    def drop_fp8_rowmajor(self) -> "DecoderWeights":
+        """Free the row-major FP8 projections of weights that pack_fp8_decode() packed: one FP8 copy,
+        read by the FP8 decode GEMM and the FP8 prefill GEMM (the scales live in
+        K.PackedWeightF8.scale).  Nothing can run K.linear_fp8 on these weights afterwards."""
+        if self.fp8_packed is None:
+            raise ValueError("drop_fp8_rowmajor needs the packed FP8 copies: pack_fp8_decode() first")
+        self.fp8_layers = [{} for _ in self.fp8_packed]   # still "fp8 weights", with no tensor left
+        self.fp8_packed_only = True
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()
         return self
 
     DECODE_PACKED = ("qkv", "o", "gate_up", "down")
@@ -600,8 +614,22 @@ class DecoderModel:
             raise ValueError(f"CFC_DECODE_FP8_GEMM={f8!r}: expected 0 or 1")
         self.decode_f8gemm = (f8 == "1" and self.fp8 and weights.device.type == "cuda" and weights.tp_size == 1
                               and all(K.f8dgemm_ok(1, s) for s in weights.projection_shapes().values()))
-        if self.decode_f8gemm:
+        # CFC_PREFILL_FP8_GEMM=1, under the same conditions: _lin, the one FP8 dispatch point (every
+        # prefill projection, and the decode steps of more than K.F8DGEMM_MAX_M rows), runs on
+        # K.linear_fp8_packed over the packed copies -- the FP8 prefill GEMM (csrc/kernels/f8pgemm.hip)
+        # above 128 rows.  With both on nothing reads the row-major FP8 copies and they are freed
+        pf8 = os.environ.get("CFC_PREFILL_FP8_GEMM", "0")
+        if pf8 not in ("0", "1"):
+            raise ValueError(f"CFC_PREFILL_FP8_GEMM={pf8!r}: expected 0 or 1")
+        self.prefill_f8gemm = (pf8 == "1" and self.fp8 and weights.device.type == "cuda" and weights.tp_size == 1
+                               and all(K.f8dgemm_ok(1, s) for s in weights.projection_shapes().values()))
+        if weights.fp8_packed_only and not (self.decode_f8gemm and self.prefill_f8gemm):
+            raise ValueError("these weights hold their FP8 projections in the packed layout only "
+                             "(drop_fp8_rowmajor): they need CFC_DECODE_FP8_GEMM=1 and CFC_PREFILL_FP8_GEMM=1")
+        if self.decode_f8gemm or self.prefill_f8gemm:
             weights.pack_fp8_decode()
+        if self.decode_f8gemm and self.prefill_f8gemm:
+            weights.drop_fp8_rowmajor()
         # prefill GEMM (packed prompt rows): "hip" = the hand-written MFMA GEMM (csrc/kernels/pgemm.hip,
         # SwiGLU fused into gate/up, reading the packed weights), "lib" = the library GEMM + silu_mul
         # (CFC_PREFILL_GEMM); CFC_PGEMM_VARIANT picks pgemm's kernel, one of K.PGEMM_VARIANTS
@@ -775,6 +803,8 @@ class DecoderModel:
     def _lin(self, i: int, name: str, x: torch.Tensor) -> torch.Tensor:
         """Projection ``name`` of layer ``i``: bf16 library GEMM, or W8A8 FP8 in fp8 mode."""
         if self.fp8:
+            if self.prefill_f8gemm and (x[0] if isinstance(x, tuple) else x).is_cuda:
+                return K.linear_fp8_packed(x, self.w.fp8_packed[i][name])
             w8, s = self.w.fp8_layers[i][name]
             return K.linear_fp8(x, w8, s)
         return F.linear(x, self.w.layers[i][name])

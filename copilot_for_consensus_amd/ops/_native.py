@@ -85,6 +85,7 @@ _KERNEL_SIGS = {
     "cfc_splitk_residual_rmsnorm_fp8": [P, I, I, I, P, P, F, P, P, P],
     "cfc_f8dgemm": [P, P, P, P, I, I, I, I, I, I, P, P, c_int64, I, P],
     "cfc_f8dgemm_pack": [P, P, I, I, I, P],
+    "cfc_f8pgemm": [P, P, P, P, I, I, I, I, P, I, P],
     "cfc_ar_region_bytes": [c_int64, P],
     "cfc_ar_alloc": [c_int64, P],
     "cfc_ar_free": [P],

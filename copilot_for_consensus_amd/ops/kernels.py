@@ -1498,6 +1498,57 @@ def f8dgemm(x8: torch.Tensor, sx: torch.Tensor, w: PackedWeightF8, epi: str = "p
     return dst
 
 
+# ------------------------------------------------ W8A8 FP8 prefill GEMM (f8pgemm.hip)
+
+def f8pgemm_ok(M: int, w) -> bool:
+    """Shapes the FP8 prefill GEMM takes: M >= 1, N % 64 == 0, K % 128 == 0 of a PackedWeightF8 (an
+    (N, K) pair asks about the shape alone), X and the padded weight under 4 GiB each."""
+    N, Kd = w.shape if isinstance(w, PackedWeightF8) else w
+    return M >= 1 and f8dgemm_ok(1, (N, Kd)) and M * Kd < 1 << 32 and (N + 127) * Kd < 1 << 32
+
+
+def f8pgemm(x8: torch.Tensor, sx: torch.Tensor, w: PackedWeightF8, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One launch of the FP8 prefill GEMM: (x8 [M, K] e4m3fn, sx [M, 1] fp32) @ w^T with both scales
+    applied, bf16 ``out`` [M, N] -- the packed weight the FP8 decode GEMM reads, whatever its bn.
+    ``out`` may be a column range of a wider buffer (unit column stride, 8-byte aligned rows)."""
+    if not isinstance(w, PackedWeightF8) or x8.dim() != 2 or x8.dtype != torch.float8_e4m3fn:
+        raise ValueError("f8pgemm: x8 must be e4m3fn [M, K] and w a PackedWeightF8")
+    M, Kd = x8.shape
+    N = w.N
+    if Kd != w.K or not f8pgemm_ok(M, w) or sx.numel() != M or sx.dtype != torch.float32:
+        raise ValueError(f"f8pgemm: x8 {tuple(x8.shape)}, sx {tuple(sx.shape)} {sx.dtype} vs weight [{w.N}, {w.K}] "
+                         "(M >= 1, N % 64 == 0, K % 128 == 0, operands under 4 GiB)")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=x8.device)
+    if (tuple(out.shape) != (M, N) or out.dtype != torch.bfloat16 or out.device != x8.device or out.stride(-1) != 1
+            or out.stride(0) % 4):
+        raise ValueError(f"f8pgemm: output {tuple(out.shape)} {out.dtype} strides {out.stride()}, expected bf16 "
+                         f"{(M, N)} with unit column stride and a row stride % 4 == 0")
+    if not x8.is_cuda:
+        xd, wd = x8.float().double(), _rowmajor_f8(w).float().double()
+        out.copy_((xd @ wd.t()) * (sx.reshape(M, 1).double() * w.scale.double()))
+        return out
+    if not x8.is_contiguous() or not sx.is_contiguous():
+        raise ValueError("f8pgemm: x8 and sx must be contiguous")
+    check(kernels().cfc_f8pgemm(x8.data_ptr(), sx.data_ptr(), w.data.data_ptr(), w.scale.data_ptr(), M, N, Kd, w.bn,
+                                out.data_ptr(), int(out.stride(0)), _stream(x8)), "cfc_f8pgemm")
+    return out
+
+
+def linear_fp8_packed(x, w: PackedWeightF8) -> torch.Tensor:
+    """linear_fp8 over the packed FP8 weight alone, no library GEMM: up to F8DGEMM_MAX_M rows on the
+    FP8 decode GEMM (bf16 epilogue at the cost model's split 1, else fp32 slabs + splitk_reduce),
+    more rows on the FP8 prefill GEMM.  ``x`` is a bf16 activation (quantised here) or an
+    already-quantised (x8, scale) pair from rmsnorm_fp8 / silu_mul_fp8."""
+    x8, sx = x if isinstance(x, tuple) else quant_fp8_rows(x)
+    M = x8.shape[0]
+    if M > F8DGEMM_MAX_M:
+        return f8pgemm(x8, sx, w)
+    if f8dgemm_config(M, w.N, w.K, w.bn)[1] == 1:
+        return f8dgemm(x8, sx, w, "bf16")
+    return splitk_reduce(f8dgemm(x8, sx, w, "part"))
+
+
 def splitk_residual_rmsnorm_fp8(part: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor,
                                 eps: float) -> tuple[torch.Tensor, torch.Tensor]:
     """residual += bf16(sum of fp32 slabs [split, M, N]); returns quant_fp8_rows(RMSNorm(residual) *

@@ -146,6 +146,17 @@ __device__ __forceinline__ uint4 fp8x8_to_bf16x8(uint2 v) {
   return r;
 }
 
+// v_mfma_f32_16x16x128_f8f6f4 of two e4m3 operands (the FP8 GEMMs, f8dgemm.hip / f8pgemm.hip): a
+// lane's 32 bytes of A and of B as two 16-byte pieces each.  cbsz = blgp = 0: both operands e4m3;
+// zero scale operands select the instruction without block scales.
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ f32x4_t f8_mfma(uint4 a0, uint4 a1, uint4 b0, uint4 b1, f32x4_t c) {
+  const i32x8_t a = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
+  const i32x8_t b = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Decode RoPE + paged KV write, shared by rope_kv_kernel (elementwise.hip) and the decode attention
 // kernel that does it in its prologue (attention.hip), so both write bit-identical caches.

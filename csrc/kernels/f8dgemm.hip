@@ -55,7 +55,9 @@
 // for this kernel the claim is reasoned, not measured.  Rows past M are clamped to row M - 1 on
 // load and never stored.
 //
-// Instruction: v_mfma_f32_16x16x128_f8f6f4 (both operands e4m3, no block scales): one instruction
+// Instruction: v_mfma_f32_16x16x128_f8f6f4 (both operands e4m3, no block scales; f8_mfma in
+// common.h, shared with the FP8 prefill GEMM f8pgemm.hip, which reads the same packed weight for
+// M > 128 so that one FP8 weight copy serves prefill and decode): one instruction
 // per 128-k block and row tile, and 2 LDS reads per 32 K flop where 16x16x32 fp8 needs 4 reads of
 // 8 bytes.  A = W fragment, B = X fragment, so a lane ends up with X row 16 t + (l & 15) at the four
 // consecutive W rows n0 + 16 w + 4 (l >> 4) + r: one 16-byte (fp32) or 8-byte (bf16) store per
@@ -78,7 +80,6 @@ namespace {
 
 typedef __attribute__((address_space(3))) void f8_lds_t;
 typedef unsigned int f8_u32x4 __attribute__((ext_vector_type(4)));
-typedef int f8_i32x8 __attribute__((ext_vector_type(8)));
 
 enum { F8_PART = 0, F8_BF16 = 1 };
 
@@ -101,13 +102,6 @@ struct F8Shape {
   static constexpr int NSX = (NSX_BASE - 2 <= 63 / XP ? NSX_BASE : 2 + 63 / XP);
   static_assert(XP >= 1 && XP * LOADERS * 8 == BM, "X stage must divide over the loader waves");
 };
-
-__device__ __forceinline__ f32x4_t f8_mfma(uint4 a0, uint4 a1, uint4 b0, uint4 b1, f32x4_t c) {
-  const f8_i32x8 a = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-  const f8_i32x8 b = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
-  // cbsz = blgp = 0: both operands e4m3; zero scale operands select the instruction without block scales
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
-}
 
 // One 1-KB LDS-DMA piece: lane l's 16 source bytes land at lds_addr + 16 l (dgemm.hip's dg_glds16:
 // inline asm so that the compiler orders nothing behind it; M0 saved and restored in the statement)
