@@ -143,6 +143,9 @@ class DecoderWeights:
         # (K.PackedWeightF8): pack_fp8_decode()
         self.fp8_packed: list[dict] | None = None
         self.fp8_packed_only = False  # row-major FP8 projections freed after packing: drop_fp8_rowmajor()
+        # opt-in W4A8 MXFP4 projections, held in the MXFP4 decode GEMM's quad layout only
+        # (K.PackedWeightMX4): to_mxfp4()
+        self.mx4_packed: list[dict] | None = None
         # second copies of the decode projections in the decode GEMM's fragment-packed layout
         # (K.PackedWeight): pack_decode()
         self.packed: list[dict] | None = None
@@ -461,10 +464,41 @@ class DecoderWeights:
             torch.cuda.empty_cache()
         return self
 
+    def to_mxfp4(self) -> "DecoderWeights":
+        """Opt-in W4A8 MXFP4 (OCP e2m1 codes + one e8m0 scale per 32 k, gfx950's block-scaled
+        MFMA): the projections to_fp8() converts, quantised once (K.quant_mxfp4_weight) and held in
+        the MXFP4 decode GEMM's packed layout ONLY -- no row-major and no bf16 copy, 4.25 bits per
+        weight; packed_bytes() reports them.  Activations are quantised per token to e4m3 at run
+        time as in the FP8 mode; norms, embeddings and the lm_head stay bf16.  One GPU (or the CPU
+        reference arithmetic) only."""
+        if self.tp_size != 1:
+            raise ValueError(f"to_mxfp4: MXFP4 weights run on one GPU only, these are TP shard {self.tp_rank} of "
+                             f"{self.tp_size}")
+        if self.quant_only or self.qlayers is not None:
+            raise ValueError("to_mxfp4: a GGUF-resident model keeps its ggml-quantized blocks; MXFP4 needs bf16 weights")
+        if self.fp8_layers is not None or self.packed is not None:
+            raise ValueError("to_mxfp4 needs the bf16 projections: not after to_fp8() or pack_decode()")
+        bad = {k: s for k, s in self.projection_shapes().items() if not K.mx4dgemm_ok(1, s)}
+        if bad:
+            raise ValueError(f"to_mxfp4: projections {bad} do not fit the MXFP4 decode GEMM (N % 64 == 0, K % 128 == 0)")
+        self.mx4_packed = []
+        for layer in self.layers:
+            q = {}
+            for name in self.FP8_PROJECTIONS:
+                q[name] = K.pack_mx4dgemm_weight(*K.quant_mxfp4_weight(layer[name]))
+                layer[name] = None
+            self.mx4_packed.append(q)
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()
+        return self
+
     DECODE_PACKED = ("qkv", "o", "gate_up", "down")
 
     def packed_bytes(self) -> int:
-        """HBM a pack_decode() adds (the projections + the lm_head, bf16)."""
+        """HBM a pack_decode() adds (the projections + the lm_head, bf16); MXFP4 weights: the bytes
+        their packed projections hold, the only copy there is."""
+        if self.mx4_packed is not None:
+            return sum(p.nbytes() for layer in self.mx4_packed for p in layer.values())
         n = sum(layer[k].numel() * 2 for layer in self.layers for k in self.DECODE_PACKED if layer.get(k) is not None)
         return n + (self.lm_head.numel() * 2 if self.lm_head is not None else 0)
 
@@ -516,6 +550,7 @@ class DecoderWeights:
         for q in self.fp8_layers or []:
             n += sum(a.numel() * a.element_size() + b.numel() * b.element_size() for a, b in q.values())
         n += sum(p.nbytes() for layer in self.fp8_packed or [] for p in layer.values())
+        n += sum(p.nbytes() for layer in self.mx4_packed or [] for p in layer.values())
         return n + sum(t.numel() * t.element_size() for t in (self.embed, self.final_norm, self.lm_head)
                        if t is not None)
 
@@ -601,7 +636,16 @@ class DecoderModel:
             mode = "splitk"
         if weights.tp_size != 1 and mode == "splitk":
             mode = "lib"
-        self.fp8 = weights.fp8_layers is not None
+        # W4A8 MXFP4 projections (weights.to_mxfp4()): decode steps of up to K.MX4DGEMM_MAX_M rows on
+        # the "mx4gemm" family of the one decode layer loop (csrc/kernels/mx4dgemm.hip), everything
+        # else through _lin on K.linear_mxfp4.  The mode has this one route: no library path, no
+        # switch.  Activations are the FP8 mode's e4m3 pairs, so self.fp8 holds for it too
+        self.mx4 = weights.mx4_packed is not None
+        if self.mx4 and (weights.tp_size != 1 or not all(
+                K.mx4dgemm_ok(1, s) for s in weights.projection_shapes().values())):
+            raise ValueError("MXFP4 weights need one GPU and projections the MXFP4 decode GEMM takes "
+                             f"(N % 64 == 0, K % 128 == 0): tp_size {weights.tp_size}, {weights.projection_shapes()}")
+        self.fp8 = weights.fp8_layers is not None or self.mx4
         if self.fp8:
             mode = "lib"          # W8A8: every projection through linear_fp8 (bf16 fused paths need bf16 weights)
         self.decode_gemm = mode
@@ -612,7 +656,7 @@ class DecoderModel:
         f8 = os.environ.get("CFC_DECODE_FP8_GEMM", "0")
         if f8 not in ("0", "1"):
             raise ValueError(f"CFC_DECODE_FP8_GEMM={f8!r}: expected 0 or 1")
-        self.decode_f8gemm = (f8 == "1" and self.fp8 and weights.device.type == "cuda" and weights.tp_size == 1
+        self.decode_f8gemm = (f8 == "1" and self.fp8 and not self.mx4 and weights.device.type == "cuda" and weights.tp_size == 1
                               and all(K.f8dgemm_ok(1, s) for s in weights.projection_shapes().values()))
         # CFC_PREFILL_FP8_GEMM=1, under the same conditions: _lin, the one FP8 dispatch point (every
         # prefill projection, and the decode steps of more than K.F8DGEMM_MAX_M rows), runs on
@@ -621,7 +665,7 @@ class DecoderModel:
         pf8 = os.environ.get("CFC_PREFILL_FP8_GEMM", "0")
         if pf8 not in ("0", "1"):
             raise ValueError(f"CFC_PREFILL_FP8_GEMM={pf8!r}: expected 0 or 1")
-        self.prefill_f8gemm = (pf8 == "1" and self.fp8 and weights.device.type == "cuda" and weights.tp_size == 1
+        self.prefill_f8gemm = (pf8 == "1" and self.fp8 and not self.mx4 and weights.device.type == "cuda" and weights.tp_size == 1
                                and all(K.f8dgemm_ok(1, s) for s in weights.projection_shapes().values()))
         if weights.fp8_packed_only and not (self.decode_f8gemm and self.prefill_f8gemm):
             raise ValueError("these weights hold their FP8 projections in the packed layout only "
@@ -801,7 +845,10 @@ class DecoderModel:
             k % 64 == 0 for k in (self.cfg.hidden, q_k, w.ffn))
 
     def _lin(self, i: int, name: str, x: torch.Tensor) -> torch.Tensor:
-        """Projection ``name`` of layer ``i``: bf16 library GEMM, or W8A8 FP8 in fp8 mode."""
+        """Projection ``name`` of layer ``i``: bf16 library GEMM, W8A8 FP8 in fp8 mode, or W4A8 on
+        the MXFP4 decode GEMM (any row count: K.linear_mxfp4) in mxfp4 mode."""
+        if self.mx4:
+            return K.linear_mxfp4(x, self.w.mx4_packed[i][name])
         if self.fp8:
             if self.prefill_f8gemm and (x[0] if isinstance(x, tuple) else x).is_cuda:
                 return K.linear_fp8_packed(x, self.w.fp8_packed[i][name])
@@ -1029,12 +1076,16 @@ class DecoderModel:
         GEMV; "dgemm" -- the hand-written bf16 decode GEMM; "splitk" -- library GEMMs with the
         split-K residual + RMSNorm reduce; "lib" -- plain library GEMMs (CPU, fp8, TP without dgemm);
         "f8gemm" -- W8A8 weights on the hand-written FP8 decode GEMM (CFC_DECODE_FP8_GEMM=1, B <= 128);
+        "mx4gemm" -- MXFP4 weights on the hand-written MXFP4 decode GEMM (B <= 128; larger batches run
+        the "lib" loop, whose projections are 128-row slices of the same kernel);
         "scratch" -- quantized-blocks-only weights at a batch the quantized kernels do not take: the
         bf16 decode GEMM on the scratch each projection is unpacked into just before (where a model
         with bf16 copies would return "dgemm", "gemv" or "splitk")."""
         small = B <= K.GEMV_MAX_M
         if self.decode_f8gemm and on_gpu and B <= K.F8DGEMM_MAX_M:
             return "f8gemm"
+        if self.mx4 and on_gpu and B <= K.MX4DGEMM_MAX_M:
+            return "mx4gemm"
         if self.w.quant_only:
             return "qgemv" if small else "qgemm" if B <= self.qgemm_max_m else "scratch"
         if on_gpu and self.decode_qgemm and K.GEMV_MAX_M < B <= self.qgemm_max_m:
@@ -1118,12 +1169,13 @@ class DecoderModel:
         ``_<family>_gate_up``) runs on the ``quant`` family ("qgemv", "qgemm" or None) where that
         takes the projection -- it returns None where it does not: no quantized copy, a shape or a
         type pairing its kernel refuses -- and otherwise on the ``base`` family ("dgemm", "gemv" or
-        "splitk") over the bf16 weights of the same layer, or "f8gemm" over the W8A8 ones."""
+        "splitk") over the bf16 weights of the same layer, "f8gemm" over the W8A8 ones or "mx4gemm" over
+        the MXFP4 ones."""
         cfg, w = self.cfg, self.w
         B = x.shape[0]
         residual = x.clone()
-        # the f8gemm family carries h as the quantised (x8, scale) pair its projections read
-        h = (K.rmsnorm_fp8 if base == "f8gemm" else K.rmsnorm)(x, w.layers[0]["attn_norm"], cfg.rms_eps)
+        # the f8gemm / mx4gemm families carry h as the quantised (x8, scale) pair their projections read
+        h = (K.rmsnorm_fp8 if base in ("f8gemm", "mx4gemm") else K.rmsnorm)(x, w.layers[0]["attn_norm"], cfg.rms_eps)
 
         roles = {r: (getattr(self, f"_{quant}_{r}") if quant else None, getattr(self, f"_{base}_{r}"))
                  for r in ("qkv", "row", "gate_up")}
@@ -1262,6 +1314,25 @@ class DecoderModel:
         wg = self.w.fp8_packed[i]["gate_up"]
         split = K.f8dgemm_config(h[0].shape[0], wg.N, wg.K, wg.bn)[1]
         gu = K.f8dgemm(*h, wg, "bf16") if split == 1 else K.splitk_reduce(K.f8dgemm(*h, wg, "part", split))
+        return K.silu_mul_fp8(gu, interleaved=self.w.gate_up_interleaved)
+
+    # -- MXFP4 decode GEMM (W4A8, B <= 128, mx4dgemm.hip) over the packed MXFP4 projections: the f8gemm
+    # family's launches and rounding points with the weight operand at 4.25 bits
+
+    def _mx4gemm_qkv(self, i, h):
+        wq = self.w.mx4_packed[i]["qkv"]
+        return K.mx4dgemm(*h, wq, "part", self.qkv_split or K.mx4dgemm_config(h[0].shape[0], wq.N, wq.K, wq.bn)[1])
+
+    def _mx4gemm_row(self, i, name, x, residual, norm_w):
+        part = K.mx4dgemm(*(x if isinstance(x, tuple) else K.quant_fp8_rows(x)), self.w.mx4_packed[i][name], "part")
+        if norm_w is self.w.final_norm:     # the last down: the step's bf16 hidden state
+            return K.splitk_residual_rmsnorm(part, residual, norm_w, self.cfg.rms_eps)
+        return K.splitk_residual_rmsnorm_fp8(part, residual, norm_w, self.cfg.rms_eps)
+
+    def _mx4gemm_gate_up(self, i, h):
+        wg = self.w.mx4_packed[i]["gate_up"]
+        split = K.mx4dgemm_config(h[0].shape[0], wg.N, wg.K, wg.bn)[1]
+        gu = K.mx4dgemm(*h, wg, "bf16") if split == 1 else K.splitk_reduce(K.mx4dgemm(*h, wg, "part", split))
         return K.silu_mul_fp8(gu, interleaved=self.w.gate_up_interleaved)
 
     # -- bf16 GEMV (B <= 4, gemm.hip): gemv_tile_kernel over the packed copy when it is the only one

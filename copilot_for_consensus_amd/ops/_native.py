@@ -86,6 +86,8 @@ _KERNEL_SIGS = {
     "cfc_f8dgemm": [P, P, P, P, I, I, I, I, I, I, P, P, c_int64, I, P],
     "cfc_f8dgemm_pack": [P, P, I, I, I, P],
     "cfc_f8pgemm": [P, P, P, P, I, I, I, I, P, I, P],
+    "cfc_mx4dgemm": [P, P, P, I, I, I, I, I, I, P, P, c_int64, I, P],
+    "cfc_mx4dgemm_pack": [P, P, P, I, I, I, P],
     "cfc_ar_region_bytes": [c_int64, P],
     "cfc_ar_alloc": [c_int64, P],
     "cfc_ar_free": [P],

@@ -1549,6 +1549,167 @@ def linear_fp8_packed(x, w: PackedWeightF8) -> torch.Tensor:
     return splitk_reduce(f8dgemm(x8, sx, w, "part"))
 
 
+# ------------------------------------------------ W4A8 MXFP4 decode GEMM (mx4dgemm.hip)
+
+MX4DGEMM_MAX_M = 128                 # rows of X one launch takes (8 MFMA row tiles)
+MX4DGEMM_BNS = (128, 112, 96, 64)    # W rows per workgroup the kernel is built for
+MX4_BYTES_PER_WEIGHT = 0.5 + 1 / 32  # a 4-bit code + an e8m0 scale per 32
+# one 16x16x128 MFMA with an 8-bit operand: 8 passes of 4 cycles at 2.4 GHz (reasoned, mx4dgemm.hip)
+MX4DGEMM_MFMA_S = 32 / 2.4e9
+
+quant_mxfp4_weight = ref.quant_mxfp4_weight     # torch code, run once at load (as quant_fp8_weight is)
+dequant_mxfp4 = ref.dequant_mxfp4
+
+
+class PackedWeightMX4:
+    """An OCP MXFP4 projection weight (e2m1 codes + one e8m0 scale per 32 k) in the MXFP4 decode
+    GEMM's quad layout for bn-row workgroups (cfc_mx4dgemm_pack: bytes [ceil(N/bn)][ceil(K/512)]
+    [bn/16][4352], codes and scale dwords side by side, padding zero codes under scale 127).  Its
+    own class: the bf16 and FP8 kernels that read packed weights refuse it by type."""
+
+    __slots__ = ("data", "N", "K", "bn")
+
+    def __init__(self, data: torch.Tensor, N: int, K: int, bn: int):
+        self.data, self.N, self.K, self.bn = data, N, K, bn
+
+    @property
+    def shape(self):
+        return (self.N, self.K)
+
+    def nbytes(self) -> int:
+        return self.data.numel()
+
+    def rowmajor(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """(codes [N, K/2], scales [N, K/32]) back out of the quad layout."""
+        return ref.unpack_mx4dgemm_weight(self.data.view(-1, -(-self.K // 512), self.bn // 16, 4352), self.N, self.K)
+
+
+def mx4dgemm_ok(M: int, w) -> bool:
+    """Shapes the MXFP4 decode GEMM takes: 1 <= M <= 128, N % 64 == 0, K % 128 == 0 of a
+    PackedWeightMX4 (an (N, K) pair asks about the shape alone)."""
+    N, Kd = w.shape if isinstance(w, PackedWeightMX4) else w
+    return 1 <= M <= MX4DGEMM_MAX_M and N > 0 and N % 64 == 0 and Kd > 0 and Kd % 128 == 0
+
+
+@functools.lru_cache(maxsize=None)
+def mx4dgemm_config(M: int, N: int, K: int, bn: int | None = None) -> tuple[int, int]:
+    """(W rows per workgroup, split-K) for one MXFP4 decode projection.  Its own cost model, not the
+    FP8 one with a factor: ceil(workgroups / CUs) rounds of the LONGER of a workgroup's stream -- its
+    W slice at 17/32 byte per weight, whole 512-k quads (a part that begins or ends inside a quad
+    loads it whole) + its rows of X from L2 at one byte -- and its matrix work, one 32-cycle MFMA
+    per wave, row tile and 128-k block with the waves four abreast; plus the fp32 slabs written and
+    read back once.  The rates are the bf16 kernel's, not fitted here."""
+    bm = 16 if M <= 16 else 32 if M <= 32 else 64 if M <= 64 else 128
+    nb = K // 128
+    best = None
+    for cand in (bn,) if bn else MX4DGEMM_BNS:
+        tiles = -(-N // cand)
+        for split in range(1, nb + 1):
+            rounds = -(-tiles * split // DGEMM_CUS)
+            blocks = -(-nb // split)                            # of the longest part
+            quads = max((((p + 1) * nb // split - 1) >> 2) - (p * nb // split >> 2) + 1 for p in range(split))
+            stream = cand * quads * 512 * MX4_BYTES_PER_WEIGHT / DGEMM_CU_RATE + bm * blocks * 128 / DGEMM_X_RATE
+            mfma = -(-(cand // 16) // 4) * (bm // 16) * blocks * MX4DGEMM_MFMA_S
+            t = rounds * max(stream, mfma)
+            if split > 1:
+                t += 2 * split * M * N * 4 / DGEMM_PART_RATE
+            if best is None or t < best[0] - 1e-12:
+                best = (t, cand, split)
+    return best[1], best[2]
+
+
+def pack_mx4dgemm_weight(codes: torch.Tensor, scales: torch.Tensor, bn: int | None = None,
+                         m: int = 128) -> PackedWeightMX4:
+    """MXFP4 W[N, K] as quant_mxfp4_weight returns it (codes uint8 [N, K/2], scales uint8 [N, K/32])
+    -> PackedWeightMX4 for bn-row workgroups (default: the width mx4dgemm_config picks for an m-row batch)."""
+    N, Kd = codes.shape[0], codes.shape[1] * 2
+    if (codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or not mx4dgemm_ok(1, (N, Kd))
+            or tuple(scales.shape) != (N, Kd // 32)):
+        raise ValueError(f"pack_mx4dgemm_weight: codes {tuple(codes.shape)} {codes.dtype}, scales {tuple(scales.shape)} "
+                         f"{scales.dtype} (uint8 [N, K/2] and [N, K/32], N % 64 == 0, K % 128 == 0)")
+    bn = bn or mx4dgemm_config(m, N, Kd)[0]
+    if bn not in MX4DGEMM_BNS:
+        raise ValueError(f"pack_mx4dgemm_weight: bn {bn} not in {MX4DGEMM_BNS}")
+    if codes.is_cuda:
+        codes, scales = codes.contiguous(), scales.contiguous()
+        out = torch.empty(-(-N // bn) * -(-Kd // 512) * (bn // 16) * 4352, dtype=torch.uint8, device=codes.device)
+        check(kernels().cfc_mx4dgemm_pack(codes.data_ptr(), scales.data_ptr(), out.data_ptr(), N, Kd, bn,
+                                          _stream(codes)), "cfc_mx4dgemm_pack")
+    else:
+        out = ref.pack_mx4dgemm_weight(codes, scales, bn).reshape(-1)
+    return PackedWeightMX4(out, N, Kd, bn)
+
+
+def mx4dgemm(x8: torch.Tensor, sx: torch.Tensor, w: PackedWeightMX4, epi: str = "part", split: int | None = None,
+             out: torch.Tensor | None = None, part: torch.Tensor | None = None) -> torch.Tensor:
+    """One launch of the MXFP4 decode GEMM: (x8 [M <= 128, K] e4m3fn, sx [M, 1] fp32) @ dequant(w)^T
+    with sx applied.  ``epi`` "part": fp32 split-K slabs ``part`` [split, M, N] (default: the split-K
+    workspace; ``split`` default: the cost model's); "bf16" (split 1): ``out`` [M, N].  ``part`` /
+    ``out`` may be column ranges of wider buffers (unit column stride, 16- / 8-byte aligned rows)."""
+    if not isinstance(w, PackedWeightMX4) or x8.dim() != 2 or x8.dtype != torch.float8_e4m3fn:
+        raise ValueError("mx4dgemm: x8 must be e4m3fn [M, K] and w a PackedWeightMX4")
+    M, Kd = x8.shape
+    N = w.N
+    if Kd != w.K or not mx4dgemm_ok(M, w) or sx.numel() != M or sx.dtype != torch.float32:
+        raise ValueError(f"mx4dgemm: x8 {tuple(x8.shape)}, sx {tuple(sx.shape)} {sx.dtype} vs weight [{w.N}, {w.K}] "
+                         f"(M <= {MX4DGEMM_MAX_M}, N % 64 == 0, K % 128 == 0)")
+    if epi not in ("part", "bf16"):
+        raise ValueError(f"mx4dgemm: epi {epi!r}: expected part or bf16")
+    if epi == "bf16":
+        if split not in (None, 1):
+            raise ValueError("mx4dgemm: the bf16 epilogue needs split 1")
+        split = 1
+    elif split is None:
+        split = part.shape[0] if part is not None else mx4dgemm_config(M, N, Kd, w.bn)[1]
+    nb = Kd // 128
+    if not 1 <= split <= nb:
+        raise ValueError(f"mx4dgemm: split {split} outside 1 .. K / 128 = {nb}")
+    dst = part if epi == "part" else out
+    if dst is None:
+        dst = (_workspace(x8.device, split * M * N)[:split * M * N].view(split, M, N) if epi == "part"
+               else torch.empty(M, N, dtype=torch.bfloat16, device=x8.device))
+    want = (split, M, N) if epi == "part" else (M, N)
+    if (tuple(dst.shape) != want or dst.dtype != (torch.float32 if epi == "part" else torch.bfloat16)
+            or dst.device != x8.device or dst.stride(-1) != 1):
+        raise ValueError(f"mx4dgemm: output {tuple(dst.shape)} {dst.dtype}, expected {want}")
+    if not x8.is_cuda:
+        xd, wd = x8.float().double(), dequant_mxfp4(*w.rowmajor()).double()
+        for p in range(split):                 # the kernel's K parts: whole 128-k blocks
+            k0, k1 = p * nb // split * 128, (p + 1) * nb // split * 128
+            y = (xd[:, k0:k1] @ wd[:, k0:k1].t()) * sx.reshape(M, 1).double()
+            dst.copy_(y) if epi == "bf16" else dst[p].copy_(y)
+        return dst
+    ldo, slab = dst.stride(-2), (dst.stride(0) if epi == "part" else 0)
+    if not x8.is_contiguous() or not sx.is_contiguous():
+        raise ValueError("mx4dgemm: x8 and sx must be contiguous")
+    check(kernels().cfc_mx4dgemm(x8.data_ptr(), sx.data_ptr(), w.data.data_ptr(), M, N, Kd, split,
+                                 0 if epi == "part" else 1, w.bn, dst.data_ptr() if epi == "part" else None,
+                                 None if epi == "part" else dst.data_ptr(), int(slab), int(ldo), _stream(x8)),
+          "cfc_mx4dgemm")
+    return dst
+
+
+def linear_mxfp4(x, w: PackedWeightMX4) -> torch.Tensor:
+    """x @ dequant(w)^T in bf16, the one dispatch point of the MXFP4 weight mode.  ``x`` is a bf16
+    activation (quantised per row here) or an (x8, scale) pair from rmsnorm_fp8 / silu_mul_fp8.  Up
+    to MX4DGEMM_MAX_M rows: one launch (bf16 epilogue at the cost model's split 1, else fp32 slabs +
+    splitk_reduce); more rows: 128-row slices of the same kernel into one output, which re-streams
+    the weights once per slice -- a quarter of the bf16 bytes each time; a tiled MXFP4 prefill GEMM
+    is not built."""
+    x8, sx = x if isinstance(x, tuple) else quant_fp8_rows(x)
+    M = x8.shape[0]
+    out = torch.empty(M, w.N, dtype=torch.bfloat16, device=x8.device)
+    for r0 in range(0, M, MX4DGEMM_MAX_M):
+        r1 = min(M, r0 + MX4DGEMM_MAX_M)
+        if mx4dgemm_config(r1 - r0, w.N, w.K, w.bn)[1] == 1:
+            mx4dgemm(x8[r0:r1], sx[r0:r1], w, "bf16", out=out[r0:r1])
+        else:
+            y = splitk_reduce(mx4dgemm(x8[r0:r1], sx[r0:r1], w, "part"), out=out[r0:r1])
+            if not y.is_cuda:                  # the CPU reduce returns a tensor of its own
+                out[r0:r1].copy_(y)
+    return out
+
+
 def splitk_residual_rmsnorm_fp8(part: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor,
                                 eps: float) -> tuple[torch.Tensor, torch.Tensor]:
     """residual += bf16(sum of fp32 slabs [split, M, N]); returns quant_fp8_rows(RMSNorm(residual) *

@@ -242,6 +242,62 @@ def unpack_f8dgemm_weight(p: torch.Tensor, N: int) -> torch.Tensor:
     return v.permute(0, 2, 5, 1, 3, 4, 6).reshape(T * NW * 16, KB * 128)[:N].contiguous().view(torch.float8_e4m3fn)
 
 
+# OCP MXFP4: e2m1 codes (bit 3 the sign, bits 2..0 index E2M1_VALUES), two per byte -- value 2 j of a
+# row in the LOW nibble of byte j, value 2 j + 1 in the high one -- and one e8m0 scale (2^(s - 127))
+# per 32 consecutive k of a row.  The same order in the quantiser, the packers and mx4dgemm.hip.
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quant_mxfp4_weight(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """W[N, K] -> (codes uint8 [N, K/2], scales uint8 [N, K/32]).  Per 32-block: scale exponent
+    floor(log2(amax)) - 2 (e2m1's emax), biased by 127, clamped to 0..254 (255 = NaN is never
+    written; an all-zero block gets 127 and zero codes); elements rounded to nearest-even onto
+    E2M1_VALUES, saturating at 6."""
+    N, K = w.shape
+    v = w.double().reshape(N, K // 32, 32)
+    amax = v.abs().amax(-1)
+    ex = torch.frexp(amax)[1] - 1                                   # floor(log2(amax)) where amax > 0
+    sc = torch.where(amax > 0, (ex - 2 + 127).clamp(0, 254), torch.full_like(ex, 127))
+    a = torch.ldexp(v.abs(), (127 - sc)[..., None])
+    # the grid's step is 0.5 below 2, 1 below 4, 2 above: torch.round rounds halves to even
+    q = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2)).clamp(max=6)
+    idx = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q / 2 + 4)).to(torch.uint8)
+    code = (idx | (((v < 0) & (idx > 0)).to(torch.uint8) << 3)).reshape(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), sc.to(torch.uint8).contiguous()
+
+
+def dequant_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """quant_mxfp4_weight's values as bf16 [N, K]: exact, a 2-bit significand times a power of two."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    lut = torch.tensor(E2M1_VALUES + tuple(-x for x in E2M1_VALUES), dtype=torch.float64, device=codes.device)
+    v = lut[torch.stack([codes & 15, codes >> 4], -1).long()].reshape(N, K // 32, 32)
+    return torch.ldexp(v, (scales.int() - 127)[..., None]).reshape(N, K).to(torch.bfloat16)
+
+
+def pack_mx4dgemm_weight(codes: torch.Tensor, scales: torch.Tensor, bn: int) -> torch.Tensor:
+    """MXFP4 W (codes [N, K/2], scales [N, K/32]) -> the MXFP4 decode GEMM's quad layout for bn-row
+    workgroups, bytes [ceil(N / bn), ceil(K / 512), bn / 16, 4352]: a record is the codes
+    [4 blocks b][64 lanes 16 g + r][16 B] = codes[bn t + 16 w + r, 256 q + 64 b + 16 g + j], then the
+    scale dwords [64 lanes][4 B], byte b = scales[bn t + 16 w + r, 16 q + 4 b + g]; rows past N and
+    blocks past K are zero codes under scale 127 (mx4dgemm.hip)."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    T, Q, NW = -(-N // bn), -(-K // 512), bn // 16
+    c = torch.zeros(T * bn, Q * 256, dtype=torch.uint8, device=codes.device)
+    s = torch.full((T * bn, Q * 16), 127, dtype=torch.uint8, device=codes.device)
+    c[:N, :K // 2], s[:N, :K // 32] = codes, scales
+    c = c.reshape(T, NW, 16, Q, 4, 4, 16).permute(0, 3, 1, 4, 5, 2, 6).reshape(T, Q, NW, 4096)   # t, q, w, b, g, r, j
+    s = s.reshape(T, NW, 16, Q, 4, 4).permute(0, 3, 1, 5, 2, 4).reshape(T, Q, NW, 256)           # t, q, w, g, r, b
+    return torch.cat([c, s], -1).contiguous()
+
+
+def unpack_mx4dgemm_weight(p: torch.Tensor, N: int, K: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """pack_mx4dgemm_weight's inverse: (codes [N, K/2], scales [N, K/32]) of the first N rows and K columns."""
+    T, Q, NW = p.shape[0], p.shape[1], p.shape[2]
+    c = p[..., :4096].reshape(T, Q, NW, 4, 4, 16, 16).permute(0, 2, 5, 1, 3, 4, 6).reshape(T * NW * 16, Q * 256)
+    s = p[..., 4096:].reshape(T, Q, NW, 4, 16, 4).permute(0, 2, 4, 1, 5, 3).reshape(T * NW * 16, Q * 16)
+    return c[:N, :K // 2].contiguous(), s[:N, :K // 32].contiguous()
+
+
 def silu_mul_interleaved(gu):
     F, G = gu.shape[-1] // 2, GU_GROUP
     v = gu.reshape(*gu.shape[:-1], F // G, 2, G).float()

@@ -57,6 +57,8 @@ class BenchPipeline:
         w = DecoderWeights.random(self.cfg, self.device, seed=1234, tp_rank=tp_rank, tp_size=tp)
         if weight_dtype == "fp8":
             w.to_fp8()           # opt-in W8A8 FP8 projections (precision trade-off, not the headline)
+        elif weight_dtype == "mxfp4":
+            w.to_mxfp4()         # opt-in W4A8 MXFP4 projections on the MXFP4 decode GEMM (one GPU)
         custom_ar = None
         if tp > 1:
             from ..parallel.custom_ar import maybe_create

@@ -116,6 +116,8 @@ class HipLLMSummarizer(Summarizer):
             self.tokenizer = synthetic_bpe(cfg.vocab_size)
         if weight_dtype == "fp8":
             w.to_fp8()           # opt-in W8A8 FP8 projections (LLM_WEIGHT_DTYPE=fp8)
+        elif weight_dtype == "mxfp4":
+            w.to_mxfp4()         # opt-in W4A8 MXFP4 projections (LLM_WEIGHT_DTYPE=mxfp4; one GPU)
         self.cfg = cfg
         self.model = cfg.name
         custom_ar = None

@@ -157,6 +157,19 @@ __device__ __forceinline__ f32x4_t f8_mfma(uint4 a0, uint4 a1, uint4 b0, uint4 b
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
 }
 
+// v_mfma_scale_f32_16x16x128_f8f6f4 with A = 32 MXFP4 values (e2m1 codes, cbsz = 4: the low four
+// dwords of the 8-dword operand, value j in bits 4 (j & 1) .. + 3 of byte j >> 1) under ONE e8m0
+// block scale -- byte SEL of the lane's own scale dword sa, picked by op_sel -- and B = 32 e4m3
+// bytes (two 16-byte pieces) under the constant scale 1.0 (e8m0 0x7f).  Lane group g's A values are
+// K = 32 g + j of the instruction, its B pieces K = 16 g + i and 64 + 16 g + i (measured; mx4dgemm.hip).
+// The scale multiplies inside the matrix unit: no VALU work per weight.
+template <int SEL>
+__device__ __forceinline__ f32x4_t mx4_mfma(uint4 a4, uint32_t sa, uint4 b0, uint4 b1, f32x4_t c) {
+  const i32x8_t a = {(int)a4.x, (int)a4.y, (int)a4.z, (int)a4.w, 0, 0, 0, 0};
+  const i32x8_t b = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 4, 0, SEL, (int)sa, 0, 0x7f7f7f7f);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Decode RoPE + paged KV write, shared by rope_kv_kernel (elementwise.hip) and the decode attention
 // kernel that does it in its prologue (attention.hip), so both write bit-identical caches.
