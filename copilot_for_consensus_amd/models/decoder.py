@@ -667,6 +667,15 @@ class DecoderModel:
             raise ValueError(f"CFC_PREFILL_FP8_GEMM={pf8!r}: expected 0 or 1")
         self.prefill_f8gemm = (pf8 == "1" and self.fp8 and not self.mx4 and weights.device.type == "cuda" and weights.tp_size == 1
                                and all(K.f8dgemm_ok(1, s) for s in weights.projection_shapes().values()))
+        # CFC_PREFILL_MX4_GEMM=1 in mxfp4 mode: _lin's calls of more than K.MX4DGEMM_MAX_M rows (every
+        # prefill projection, decode steps wider than 128) make one launch of the MXFP4 prefill GEMM
+        # (csrc/kernels/mx4pgemm.hip) on the same packed copy.  Off by default (unset / 0): 128-row
+        # slices of the decode kernel, as before
+        pm4 = os.environ.get("CFC_PREFILL_MX4_GEMM", "0")
+        if pm4 not in ("0", "1"):
+            raise ValueError(f"CFC_PREFILL_MX4_GEMM={pm4!r}: expected 0 or 1")
+        self.prefill_mx4gemm = (pm4 == "1" and self.mx4 and weights.device.type == "cuda"
+                                and all(K.mx4pgemm_ok(1, s) for s in weights.projection_shapes().values()))
         if weights.fp8_packed_only and not (self.decode_f8gemm and self.prefill_f8gemm):
             raise ValueError("these weights hold their FP8 projections in the packed layout only "
                              "(drop_fp8_rowmajor): they need CFC_DECODE_FP8_GEMM=1 and CFC_PREFILL_FP8_GEMM=1")
@@ -846,9 +855,10 @@ class DecoderModel:
 
     def _lin(self, i: int, name: str, x: torch.Tensor) -> torch.Tensor:
         """Projection ``name`` of layer ``i``: bf16 library GEMM, W8A8 FP8 in fp8 mode, or W4A8 on
-        the MXFP4 decode GEMM (any row count: K.linear_mxfp4) in mxfp4 mode."""
+        the MXFP4 GEMMs in mxfp4 mode (K.linear_mxfp4: the decode kernel up to 128 rows; above, its
+        128-row slices, or with CFC_PREFILL_MX4_GEMM=1 one launch of the prefill kernel)."""
         if self.mx4:
-            return K.linear_mxfp4(x, self.w.mx4_packed[i][name])
+            return K.linear_mxfp4(x, self.w.mx4_packed[i][name], tiled=self.prefill_mx4gemm)
         if self.fp8:
             if self.prefill_f8gemm and (x[0] if isinstance(x, tuple) else x).is_cuda:
                 return K.linear_fp8_packed(x, self.w.fp8_packed[i][name])
@@ -1077,7 +1087,8 @@ class DecoderModel:
         split-K residual + RMSNorm reduce; "lib" -- plain library GEMMs (CPU, fp8, TP without dgemm);
         "f8gemm" -- W8A8 weights on the hand-written FP8 decode GEMM (CFC_DECODE_FP8_GEMM=1, B <= 128);
         "mx4gemm" -- MXFP4 weights on the hand-written MXFP4 decode GEMM (B <= 128; larger batches run
-        the "lib" loop, whose projections are 128-row slices of the same kernel);
+        the "lib" loop, whose projections are 128-row slices of the same kernel, or with
+        CFC_PREFILL_MX4_GEMM=1 one launch each of the MXFP4 prefill GEMM);
         "scratch" -- quantized-blocks-only weights at a batch the quantized kernels do not take: the
         bf16 decode GEMM on the scratch each projection is unpacked into just before (where a model
         with bf16 copies would return "dgemm", "gemv" or "splitk")."""

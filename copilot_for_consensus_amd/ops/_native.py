@@ -88,6 +88,7 @@ _KERNEL_SIGS = {
     "cfc_f8pgemm": [P, P, P, P, I, I, I, I, P, I, P],
     "cfc_mx4dgemm": [P, P, P, I, I, I, I, I, I, P, P, c_int64, I, P],
     "cfc_mx4dgemm_pack": [P, P, P, I, I, I, P],
+    "cfc_mx4pgemm": [P, P, P, I, I, I, I, P, I, P],
     "cfc_ar_region_bytes": [c_int64, P],
     "cfc_ar_alloc": [c_int64, P],
     "cfc_ar_free": [P],

@@ -1689,15 +1689,55 @@ def mx4dgemm(x8: torch.Tensor, sx: torch.Tensor, w: PackedWeightMX4, epi: str = 
     return dst
 
 
-def linear_mxfp4(x, w: PackedWeightMX4) -> torch.Tensor:
+def mx4pgemm_ok(M: int, w) -> bool:
+    """Shapes the MXFP4 prefill GEMM takes: M >= 1, the decode kernel's N % 64 == 0 and K % 128 == 0
+    of a PackedWeightMX4 (an (N, K) pair asks about the shape alone), X and the padded quad layout
+    under 4 GiB each."""
+    N, Kd = w.shape if isinstance(w, PackedWeightMX4) else w
+    return (M >= 1 and mx4dgemm_ok(1, (N, Kd)) and M * Kd < 1 << 32
+            and -(-(N + 127) // 16) * -(-Kd // 512) * 4352 < 1 << 32)
+
+
+def mx4pgemm(x8: torch.Tensor, sx: torch.Tensor, w: PackedWeightMX4, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One launch of the MXFP4 prefill GEMM (mx4pgemm.hip): (x8 [M, K] e4m3fn, sx [M, 1] fp32) @
+    dequant(w)^T with sx applied, bf16 ``out`` [M, N] -- the packed weight the MXFP4 decode GEMM reads,
+    whatever its bn.  ``out`` may be a column range of a wider buffer (unit column stride, 8-byte
+    aligned rows)."""
+    if not isinstance(w, PackedWeightMX4) or x8.dim() != 2 or x8.dtype != torch.float8_e4m3fn:
+        raise ValueError("mx4pgemm: x8 must be e4m3fn [M, K] and w a PackedWeightMX4")
+    M, Kd = x8.shape
+    N = w.N
+    if Kd != w.K or not mx4pgemm_ok(M, w) or sx.numel() != M or sx.dtype != torch.float32:
+        raise ValueError(f"mx4pgemm: x8 {tuple(x8.shape)}, sx {tuple(sx.shape)} {sx.dtype} vs weight [{w.N}, {w.K}] "
+                         "(M >= 1, N % 64 == 0, K % 128 == 0, operands under 4 GiB)")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=x8.device)
+    if (tuple(out.shape) != (M, N) or out.dtype != torch.bfloat16 or out.device != x8.device or out.stride(-1) != 1
+            or out.stride(0) % 4):
+        raise ValueError(f"mx4pgemm: output {tuple(out.shape)} {out.dtype} strides {out.stride()}, expected bf16 "
+                         f"{(M, N)} with unit column stride and a row stride % 4 == 0")
+    if not x8.is_cuda:
+        xd, wd = x8.float().double(), dequant_mxfp4(*w.rowmajor()).double()
+        out.copy_((xd @ wd.t()) * sx.reshape(M, 1).double())
+        return out
+    if not x8.is_contiguous() or not sx.is_contiguous():
+        raise ValueError("mx4pgemm: x8 and sx must be contiguous")
+    check(kernels().cfc_mx4pgemm(x8.data_ptr(), sx.data_ptr(), w.data.data_ptr(), M, N, Kd, w.bn, out.data_ptr(),
+                                 int(out.stride(0)), _stream(x8)), "cfc_mx4pgemm")
+    return out
+
+
+def linear_mxfp4(x, w: PackedWeightMX4, tiled: bool = False) -> torch.Tensor:
     """x @ dequant(w)^T in bf16, the one dispatch point of the MXFP4 weight mode.  ``x`` is a bf16
     activation (quantised per row here) or an (x8, scale) pair from rmsnorm_fp8 / silu_mul_fp8.  Up
-    to MX4DGEMM_MAX_M rows: one launch (bf16 epilogue at the cost model's split 1, else fp32 slabs +
-    splitk_reduce); more rows: 128-row slices of the same kernel into one output, which re-streams
-    the weights once per slice -- a quarter of the bf16 bytes each time; a tiled MXFP4 prefill GEMM
-    is not built."""
+    to MX4DGEMM_MAX_M rows: one launch of the decode GEMM (bf16 epilogue at the cost model's split 1,
+    else fp32 slabs + splitk_reduce).  More rows: with ``tiled`` one launch of the MXFP4 prefill GEMM
+    (mx4pgemm); without it 128-row slices of the decode kernel into one output, which re-streams the
+    weights once per slice."""
     x8, sx = x if isinstance(x, tuple) else quant_fp8_rows(x)
     M = x8.shape[0]
+    if tiled and M > MX4DGEMM_MAX_M:
+        return mx4pgemm(x8, sx, w)
     out = torch.empty(M, w.N, dtype=torch.bfloat16, device=x8.device)
     for r0 in range(0, M, MX4DGEMM_MAX_M):
         r1 = min(M, r0 + MX4DGEMM_MAX_M)
