@@ -2317,10 +2317,24 @@ def _merge_candidates(cv: torch.Tensor, ci: torch.Tensor, k: int):
 
 
 def knn_topk(X, Q, k: int, xnorm2=None, qnorm2=None, alive=None, row_lo: int = 0, N: int | None = None):
-    """Fused flat scan + top-k (knn.hip knn_topk_kernel) over rows [row_lo, N) of X for <= 16
-    queries: (scores [nq, k] descending, row indices [nq, k]); the [nq, N] scores never reach HBM."""
+    """Fused flat scan + top-k over rows [row_lo, N) of X for any number of queries, k <= 256:
+    (scores [nq, k] descending, row indices [nq, k]); the [nq, N] scores never reach HBM.  Up to 16
+    queries run knn.hip's knn_topk_kernel / knn_topk_stream_kernel; more run knn_topk_many_kernel,
+    one pass over the index per tile of 32-128 queries (``cfc_knn_many_plan``) instead of one per 16.
+    Rows masked by ``alive`` never come back from the many-query kernel: with fewer than k live rows
+    its tail is -inf / -1."""
     N = X.shape[0] if N is None else N
     nq = Q.shape[0]
+    if X.is_cuda and nq > 16:
+        plan = torch.empty(4, dtype=torch.int32)     # query tile, span rows, slots per query, spans
+        check(kernels().cfc_knn_many_plan(nq, k, X.shape[1], N - row_lo, plan.data_ptr()), "cfc_knn_many_plan")
+        spans = int(plan[3])
+        cv = torch.empty(nq, spans * k, dtype=torch.float32, device=X.device)
+        ci = torch.empty(nq, spans * k, dtype=torch.int64, device=X.device)
+        check(kernels().cfc_knn_topk_many(X.data_ptr(), Q.data_ptr(), N, row_lo, nq, X.shape[1], _p(xnorm2),
+                                          _p(qnorm2), _p(alive), k, cv.data_ptr(), ci.data_ptr(), _stream(X)),
+              "cfc_knn_topk_many")
+        return _merge_candidates(cv, ci, min(k, N - row_lo))
     if not X.is_cuda:
         sc = ref.knn_scores(X[row_lo:N], Q, None if xnorm2 is None else xnorm2[row_lo:N], qnorm2)
         if alive is not None:

@@ -362,8 +362,8 @@ class HipFlatIndex(VectorStore):
         else:
             Qn = Q.contiguous()
             qn2 = Qn.float().pow(2).sum(1)
-        if Q.is_cuda and nq <= 16 and k <= 256:
-            # fused scan + top-k: only k candidates per 1024-row chunk leave the CUs
+        if Q.is_cuda and k <= 256:
+            # fused scan + top-k for any nq: only k candidates per chunk / span leave the CUs
             return K.knn_topk(self._X, Qn, k, self._norm2 if self.metric == "l2" else None, qn2,
                               self._alive if self._dead else None, row_lo=lo, N=hi)
         xn2 = self._norm2[lo:hi] if self.metric == "l2" else None
@@ -403,8 +403,11 @@ class HipFlatIndex(VectorStore):
                 return [[] for _ in range(len(query_vectors))]
             Q = _as_matrix(query_vectors, self.dim)
             outs = []
-            for s in range(0, Q.shape[0], 16):
-                v, i = self.search(Q[s:s + 16], min(top_k, self.count()))
+            # the fused GPU scan takes the whole batch (one pass per query tile); the CPU and the
+            # k > 256 score-matrix path keep 16-query slices
+            step = max(1, Q.shape[0]) if self.device.type == "cuda" and top_k <= 256 else 16
+            for s in range(0, Q.shape[0], step):
+                v, i = self.search(Q[s:s + step], min(top_k, self.count()))
                 outs.extend(self._to_results(v, i, with_vectors))
             return outs
 
@@ -648,13 +651,8 @@ class HipIVFIndex(HipFlatIndex):
             return self._search_ref(Qn, qn2, probe, k)
         cv, ci = K.ivf_topk(self._X, Qn, probe, self._list_off_t, self._maxc, k, xn2, qn2, alive)
         if self._n > self._trained_n:       # the unsorted tail, for every query
-            tv, ti = [], []
-            for s in range(0, Qn.shape[0], 16):
-                v, i = K.knn_topk(self._X, Qn[s:s + 16], k, xn2, None if qn2 is None else qn2[s:s + 16], alive,
-                                  row_lo=self._trained_n, N=self._n)
-                tv.append(v)
-                ti.append(i)
-            cv, ci = torch.cat([cv, torch.cat(tv)], 1), torch.cat([ci, torch.cat(ti)], 1)
+            tv, ti = K.knn_topk(self._X, Qn, k, xn2, qn2, alive, row_lo=self._trained_n, N=self._n)
+            cv, ci = torch.cat([cv, tv], 1), torch.cat([ci, ti], 1)
         return K.topk(cv, min(k, self.count()), ci)
 
     def _search_ref(self, Qn, qn2, probe, k):

@@ -15,6 +15,9 @@
 //     so only k candidates per (query, chunk) reach HBM (never the [nq, N] score matrix); the
 //     IVF form takes (query, probed list, chunk) work items from a device list-offset table in
 //     one launch.  The candidates are merged by cfc_topk_pass.
+//   * cfc_knn_topk_many: the fused scan for more than 16 queries: one pass over the index per tile
+//     of 32-128 queries (cfc_knn_many_plan), X staged once per workgroup through an LDS-DMA ring,
+//     scores filtered from the MFMA accumulators into per-query LDS candidate buffers.
 //   * cfc_l2_normalize: rows -> unit length (+ fp32 norms), used on insert for cosine.
 //   * cfc_pool: masked mean / CLS pooling over varlen sequences (+ optional L2 normalise):
 //     the SentenceTransformer Pooling+Normalize modules.
@@ -292,39 +295,43 @@ __global__ void __launch_bounds__(256) knn_topk_kernel(const uint16_t* __restric
 // skipped: the buffer already holds k keys >= it, so the result is exact up to tie order.
 constexpr int KS_SUB = 256, KS_CAP = 512, KS_SPAN = 16384;
 
-// keys held KS_CAP / 64 per lane (entry lane + 64 j; 0 = empty): the exact kk-th largest
+// keys held NJ per lane (entry lane + 64 j; 0 = empty): the exact kk-th largest
+template <int NJ>
 __device__ __forceinline__ uint32_t ks_kth(const uint32_t* key, int kk) {
   uint32_t thr = 0;
   for (int b = 31; b >= 0; --b) {
     const uint32_t cand = thr | (1u << b);
     int c = 0;
 #pragma unroll
-    for (int j = 0; j < KS_CAP / 64; ++j) c += __popcll(__ballot(key[j] >= cand));
+    for (int j = 0; j < NJ; ++j) c += __popcll(__ballot(key[j] >= cand));
     if (c >= kk) thr = cand;                 // wave-uniform decision
   }
   return thr;
 }
 
-// Cut a query's buffer (cnt > kk entries) to its exact top kk, in place (wave-level; every entry is
-// in registers before the first write).  Returns the kk-th largest key (the new threshold).
-__device__ __forceinline__ uint32_t ks_cut(uint32_t* bk, uint32_t* br, int cnt, int kk) {
+// Cut a query's buffer (kk < cnt <= 64 NJ entries; rows as RT) to its exact top kk, in place
+// (wave-level; every entry is in registers before the first write).  Returns the kk-th largest
+// key (the new threshold).
+template <int NJ, typename RT>
+__device__ __forceinline__ uint32_t ks_cut(uint32_t* bk, RT* br, int cnt, int kk) {
   const int lane = threadIdx.x & 63;
-  uint32_t key[KS_CAP / 64], row[KS_CAP / 64];
+  uint32_t key[NJ];
+  RT row[NJ];
 #pragma unroll
-  for (int j = 0; j < KS_CAP / 64; ++j) {
+  for (int j = 0; j < NJ; ++j) {
     const int i = lane + 64 * j;
     key[j] = i < cnt ? bk[i] : 0u;
-    row[j] = i < cnt ? br[i] : 0u;
+    row[j] = i < cnt ? br[i] : (RT)0;
   }
-  const uint32_t thr = ks_kth(key, kk);
+  const uint32_t thr = ks_kth<NJ>(key, kk);
   int gt = 0;
 #pragma unroll
-  for (int j = 0; j < KS_CAP / 64; ++j) gt += __popcll(__ballot(key[j] > thr));
+  for (int j = 0; j < NJ; ++j) gt += __popcll(__ballot(key[j] > thr));
   const uint32_t need = (uint32_t)(kk - gt);
   const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   uint32_t base_gt = 0, base_eq = 0;
 #pragma unroll
-  for (int j = 0; j < KS_CAP / 64; ++j) {
+  for (int j = 0; j < NJ; ++j) {
     const bool g = key[j] > thr, e = key[j] == thr && key[j] != 0u;
     const uint64_t bg = __ballot(g), be = __ballot(e);
     int slot = -1;
@@ -410,7 +417,7 @@ __global__ void __launch_bounds__(512) knn_topk_stream_kernel(const uint16_t* __
           cnt[t] += __popcll(b);
         }
         if (cnt[t] > KS_CAP - KS_SUB) {        // the next sub-chunk might not fit: cut to k (k <= 256)
-          thr[t] = ks_cut(qk, qr, cnt[t], k);
+          thr[t] = ks_cut<KS_CAP / 64>(qk, qr, cnt[t], k);
           cnt[t] = k;
         }
       }
@@ -425,7 +432,7 @@ __global__ void __launch_bounds__(512) knn_topk_stream_kernel(const uint16_t* __
       uint32_t* qr = br + qi * KS_CAP;
       int n = cnt[t];
       if (n > k) {
-        ks_cut(qk, qr, n, k);
+        ks_cut<KS_CAP / 64>(qk, qr, n, k);
         n = k;
       }
       const size_t o = ((size_t)qi * gridDim.x + blockIdx.x) * k;
@@ -433,6 +440,210 @@ __global__ void __launch_bounds__(512) knn_topk_stream_kernel(const uint16_t* __
         out_v[o + s2] = s2 < n ? key2f(qk[s2]) : -INFINITY;
         out_i[o + s2] = s2 < n ? (int64_t)lo + qr[s2] : -1;
       }
+    }
+  }
+}
+
+// ------------------------------------------------------------------ many-query scan + top-k (nq > 16)
+// One pass over the index for a TILE of qt = 32 / 64 / 128 queries: grid = (spans, query tiles), one
+// 8-wave workgroup per CU owning the whole 160 KB of LDS.
+//
+//   * X is read from HBM once per workgroup, by LDS-DMA (1-KB pieces, every wave issues P of them
+//     per stage) into a ring of NS stages of RS rows; NS - 1 stages (32-64 KB per CU, the HBM
+//     latency x 10 B/clk per CU) are in flight while one is scored.  No wave loads X itself, so
+//     the index costs one global read per row however many waves score it.  The row image is
+//     XOR-swizzled through the SOURCE address (16-byte chunk j of row r at chunk j ^ (r & 7)):
+//     rows are a multiple of 256 B apart, and the 8 lanes one ds_read_b128 clock serves then hit 8
+//     different chunks.
+//   * A wave keeps the B fragments of TQ 16-query groups in registers for the whole span (4 KC
+//     VGPRs each: TQ = 2 up to dim 512 = 128 VGPRs, TQ = 1 above) and reads A fragments (16 rows)
+//     from the ring: 1 KB of LDS per TQ MFMAs.  Waves are laid out qt / (16 TQ) query columns x
+//     the rest as row-group lanes.  Budget at dim 384, qt 128, per 16-row group (12 KB = 1200 clk of
+//     a CU's HBM share): 96 MFMAs x 16 clk over 4 SIMDs = 384 clk; LDS 4 waves x 12 KB read + 12 KB
+//     DMA written = 60 KB / 128 B/clk = 480 clk (TQ = 1 would be 864).  At dim 1024 (TQ = 1): HBM
+//     3200 clk, MFMA 1024, LDS 2304.  With a small tile some waves only issue DMA; the tile's MFMA
+//     work is then small too (qt 32, dim 1024: 64 MFMAs on 2 SIMDs = 512 clk of 3200).
+//   * Scores leave the accumulators through a per-query threshold: a key above it takes a slot
+//     (LDS atomic) in the query's candidate buffer of `cap` (key u32, row-in-span u16) entries.
+//     After every stage, buffers holding more than cap - RS entries are cut to their exact top k
+//     by ks_cut and the threshold becomes the k-th key.  A stage adds at most RS entries to one
+//     buffer and a cut leaves k <= cap - RS, so a slot is always free: no candidate is dropped
+//     whatever the order of the data (ascending scores only cost a cut every (cap - RS - k) / RS
+//     stages).  Keys equal to the threshold after a cut are skipped: k keys >= it are held.
+//   * LDS: ring NS x RS x dim x 2 B (64 KB; 72 KB at dim 384 / 768; 96 KB at dim 1024) + 1 KB of
+//     counts and thresholds + qt x cap x 6 B.  km_plan picks the largest tile the rest holds with
+//     cap >= k + RS + 16: dim 384 -> qt 128 up to k = 68, qt 64 up to k = 184, qt 32 above.
+//   * The L2 metric's row norms and the alive bytes of passing rows are ordinary loads: the wait the
+//     compiler puts behind them is in-order, so it also drains the ring.  Reasoned, not measured:
+//     the L2 scan runs nearer one stage in flight than NS - 1.
+//   * Two barriers per stage: A (stage landed: counted vmcnt, the younger stages stay in flight;
+//     every append of the last stage visible) and B (cuts done).  Waves never wait on vmcnt(0).
+constexpr int KM_LDS = 160 * 1024;
+constexpr int KM_MAXQT = 128;
+constexpr int KM_MAXSPAN = 65536;              // rows in a span: offsets are uint16
+constexpr int km_rs(int kc) { return kc <= 12 ? 32 : 16; }                              // rows per stage
+constexpr int km_ns(int kc) { return kc == 4 ? 8 : (kc == 8 || kc == 16) ? 4 : 3; }     // ring stages
+
+typedef __attribute__((address_space(3))) void km_lds_t;
+
+// One 1-KB LDS-DMA piece (lane l's 16 bytes land at lds_addr + 16 l), as in dgemm.hip.
+__device__ __forceinline__ void km_glds16(const void* gsrc, uint32_t lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(gsrc), "s"(lds_addr)
+               : "memory");
+}
+
+__device__ __forceinline__ uint32_t km_cut(uint32_t* bk, uint16_t* br, int cnt, int kk, int cap) {
+  switch ((cap + 63) >> 6) {
+    case 1: return ks_cut<1>(bk, br, cnt, kk);
+    case 2: return ks_cut<2>(bk, br, cnt, kk);
+    case 3: return ks_cut<3>(bk, br, cnt, kk);
+    case 4: return ks_cut<4>(bk, br, cnt, kk);
+    case 5: return ks_cut<5>(bk, br, cnt, kk);
+    case 6: return ks_cut<6>(bk, br, cnt, kk);
+    case 7: return ks_cut<7>(bk, br, cnt, kk);
+    default: return ks_cut<8>(bk, br, cnt, kk);   // km_plan: cap <= 512
+  }
+}
+
+template <int KC>
+__global__ void __launch_bounds__(512) knn_topk_many_kernel(const uint16_t* __restrict__ X,
+                                                            const uint16_t* __restrict__ Q, int N, int nq,
+                                                            const float* __restrict__ xnorm2,
+                                                            const float* __restrict__ qnorm2,
+                                                            const uint8_t* __restrict__ alive, int k, int row_lo,
+                                                            int qt, int span, int cap, float* __restrict__ out_v,
+                                                            int64_t* __restrict__ out_i) {
+  constexpr int D = KC * 32, TQ = KC <= 16 ? 2 : 1, RS = km_rs(KC), NS = km_ns(KC);
+  constexpr int CH = KC * 4;                   // 16-byte chunks per row
+  constexpr int SB = RS * CH * 16;             // bytes per stage
+  constexpr int P = SB / 1024 / 8;             // DMA pieces per wave per stage
+  static_assert(P * 8 * 1024 == SB && (NS - 2) * P <= 63, "stage = 8 waves x P pieces; vmcnt is 6 bits");
+  __shared__ __attribute__((aligned(16))) char smem[KM_LDS];
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + NS * SB);     // [KM_MAXQT]
+  uint32_t* thr = cnt + KM_MAXQT;                                  // [KM_MAXQT]
+  uint32_t* bk = thr + KM_MAXQT;                                   // [qt][cap]
+  uint16_t* br = reinterpret_cast<uint16_t*>(bk + qt * cap);       // [qt][cap]
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = lane & 15, g = lane >> 4;
+  const int lo = row_lo + blockIdx.x * span, hi = min(N, lo + span);
+  const int q0 = blockIdx.y * qt;
+  const int WQ = qt / (16 * TQ), qc = w % WQ, rg = w / WQ, NRG = 8 / WQ;
+
+  for (int i = threadIdx.x; i < 2 * KM_MAXQT; i += 512) cnt[i] = 0u;  // counts and thresholds
+
+  // this wave's queries: local ql[t], fragments in registers for the whole span
+  bf16x8_t qf[TQ][KC];
+  int ql[TQ];
+  bool qv[TQ];
+  float qn[TQ];
+#pragma unroll
+  for (int t = 0; t < TQ; ++t) {
+    ql[t] = (qc * TQ + t) * 16 + col;
+    qv[t] = q0 + ql[t] < nq;
+    const uint16_t* qr = Q + (size_t)(qv[t] ? q0 + ql[t] : 0) * D;
+#pragma unroll
+    for (int c = 0; c < KC; ++c)
+      qf[t][c] = as_bf16x8(qv[t] ? *reinterpret_cast<const uint4*>(qr + 32 * c + 8 * g) : make_uint4(0, 0, 0, 0));
+    qn[t] = (qnorm2 && qv[t]) ? qnorm2[q0 + ql[t]] : 0.f;
+  }
+
+  // DMA: piece w P + p of a stage is LDS chunks [64 (w P + p), + 64); this lane's chunk sits in
+  // stage row prow[p] and comes from source chunk (chunk in row) ^ (row & 7)
+  int prow[P], pcol[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int L = (w * P + p) * 64 + lane;
+    prow[p] = L / CH;
+    pcol[p] = ((L % CH) ^ (prow[p] & 7)) * 8;
+  }
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(km_lds_t*)smem + w * P * 1024);
+  // rows past the span's end re-read row N - 1 (never scored): every stage issues the same P
+  // loads, so the counted waits below hold in the tail too, and no read goes past N
+  auto issue = [&](int st) {
+    const uint32_t dst = lds0 + (st % NS) * SB;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const int r = min(lo + st * RS + prow[p], N - 1);
+      km_glds16(X + (size_t)r * D + pcol[p], dst + p * 1024);
+    }
+  };
+  const int nst = (hi - lo + RS - 1) / RS;
+#pragma unroll
+  for (int s = 0; s < NS - 1; ++s) issue(s);
+
+  for (int s = 0; s < nst; ++s) {
+    // A: stage s has landed (the NS - 2 younger stages stay in flight) and stage s - 1 is scored
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"((NS - 2) * P) : "memory");
+    issue(s + NS - 1);                           // into the slot stage s - 1 was read from
+    for (int qi = w; qi < qt; qi += 8) {
+      const int n = min(__builtin_amdgcn_readfirstlane((int)cnt[qi]), cap);
+      if (n > cap - RS) {
+        const uint32_t t = km_cut(bk + qi * cap, br + qi * cap, n, k, cap);
+        if (lane == 0) { thr[qi] = t; cnt[qi] = (uint32_t)k; }
+      }
+    }
+    // B: cuts done, thresholds visible
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    uint32_t th[TQ];
+#pragma unroll
+    for (int t = 0; t < TQ; ++t) th[t] = thr[ql[t]];
+    const char* sx = smem + (s % NS) * SB;
+    const int s0 = lo + s * RS;
+    for (int grp = rg; grp < RS / 16; grp += NRG) {
+      const char* arow = sx + (grp * 16 + col) * (CH * 16);
+      f32x4_t acc[TQ];
+#pragma unroll
+      for (int t = 0; t < TQ; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        const uint4 a = *reinterpret_cast<const uint4*>(arow + (((4 * c + g) ^ (col & 7)) << 4));
+#pragma unroll
+        for (int t = 0; t < TQ; ++t)
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a), qf[t][c], acc[t], 0, 0, 0);
+      }
+      const int rb = s0 + grp * 16 + 4 * g;
+      float xn[4] = {0.f, 0.f, 0.f, 0.f};
+      if (xnorm2) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xn[i] = xnorm2[min(rb + i, N - 1)];
+      }
+#pragma unroll
+      for (int t = 0; t < TQ; ++t) {
+        if (!qv[t]) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int row = rb + i;
+          float v = acc[t][i];
+          if (xnorm2) v = -(xn[i] + qn[t] - 2.f * v);
+          const uint32_t key = f2key(v);
+          if (row < hi && key > th[t] && (!alive || alive[row])) {
+            const uint32_t slot = atomicAdd(&cnt[ql[t]], 1u);
+            if (slot < (uint32_t)cap) {            // always: see the header
+              bk[ql[t] * cap + slot] = key;
+              br[ql[t] * cap + slot] = (uint16_t)(row - lo);
+            }
+          }
+        }
+      }
+    }
+  }
+  // the DMA still in flight targets the ring only; drain it before the workgroup's LDS is released
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  for (int qi = w; qi < qt && q0 + qi < nq; qi += 8) {
+    uint32_t* qk = bk + qi * cap;
+    uint16_t* qr = br + qi * cap;
+    int n = min(__builtin_amdgcn_readfirstlane((int)cnt[qi]), cap);
+    if (n > k) {
+      km_cut(qk, qr, n, k, cap);
+      n = k;
+    }
+    const size_t o = ((size_t)(q0 + qi) * gridDim.x + blockIdx.x) * k;
+    for (int s2 = lane; s2 < k; s2 += 64) {
+      out_v[o + s2] = s2 < n ? key2f(qk[s2]) : -INFINITY;
+      out_i[o + s2] = s2 < n ? (int64_t)lo + qr[s2] : -1;
     }
   }
 }
@@ -615,6 +826,63 @@ CFC_API int cfc_knn_topk(const void* X, const void* Q, int N, int row_lo, int nq
   }
   return knn_topk_dispatch(dim, X, Q, N, nq, xnorm2, qnorm2, alive, k, row_lo, nullptr, 1, 1, nullptr, nch, out_v,
                            out_i, nch, nq, rows, stream);
+}
+
+namespace {
+struct KmPlan { int qt, span, cap, nspans; };
+
+// Tile, span and candidate slots of knn_topk_many_kernel for nq queries, top-k, dim and `rows` rows
+// to scan (the kernel's header has the LDS budget).  qt: the smallest tile that holds all nq
+// queries, else the largest the LDS left by the ring holds with cap >= k + RS + 16 (k <= 256 always
+// fits qt = 32).  span: about four workgroups per CU, but long enough that the k candidates a
+// span emits stay under ~3 % of its rows, and at most KM_MAXSPAN.
+bool km_plan(int nq, int k, int dim, long rows, KmPlan* p) {
+  const int kc = dim / 32;
+  if (dim % 32 != 0 || (kc != 4 && kc != 8 && kc != 12 && kc != 16 && kc != 24 && kc != 32)) return false;
+  if (nq < 1 || k < 1 || k > 256 || rows < 1) return false;
+  const int rs = km_rs(kc);
+  const int room = KM_LDS - km_ns(kc) * rs * dim * 2 - 2 * KM_MAXQT * 4;
+  int qt = 32;
+  for (int t = 64; t <= KM_MAXQT; t *= 2)
+    if (qt < nq && room / (t * 6) >= k + rs + 16) qt = t;
+  const int tiles = (nq + qt - 1) / qt;
+  long span = (rows * tiles + 1023) / 1024;
+  const long lo = 32L * k > 1024 ? 32L * k : 1024;
+  span = span < lo ? lo : span > KM_MAXSPAN ? KM_MAXSPAN : span;
+  span = (span + 63) / 64 * 64;
+  const int cap = room / (qt * 6) > 512 ? 512 : room / (qt * 6);
+  *p = KmPlan{qt, (int)span, cap & ~1, (int)((rows + span - 1) / span)};
+  return true;
+}
+}  // namespace
+
+// Plan of cfc_knn_topk_many: out = {query tile, span rows, candidate slots per query, spans}.
+CFC_API int cfc_knn_many_plan(int nq, int k, int dim, int64_t rows, int* out) {
+  KmPlan p;
+  if (!km_plan(nq, k, dim, (long)rows, &p)) return -1;
+  out[0] = p.qt; out[1] = p.span; out[2] = p.cap; out[3] = p.nspans;
+  return 0;
+}
+
+// Flat index, rows [row_lo, N), any nq >= 1 (meant for nq > 16), k <= 256: one pass over the index
+// per query tile.  Candidates out [nq][spans][k] (spans from cfc_knn_many_plan(nq, k, dim, N - row_lo);
+// unsorted, -inf / -1 padding; merge with cfc_topk_pass).  Dead rows (alive == 0) are never candidates.
+CFC_API int cfc_knn_topk_many(const void* X, const void* Q, int N, int row_lo, int nq, int dim, const float* xnorm2,
+                              const float* qnorm2, const uint8_t* alive, int k, float* out_v, int64_t* out_i,
+                              hipStream_t stream) {
+  KmPlan p;
+  if (row_lo < 0 || N <= row_lo || !km_plan(nq, k, dim, (long)N - row_lo, &p)) return -1;
+  const dim3 grid(p.nspans, (nq + p.qt - 1) / p.qt);
+#define KM(KC) \
+  case KC: \
+    knn_topk_many_kernel<KC><<<grid, 512, 0, stream>>>((const uint16_t*)X, (const uint16_t*)Q, N, nq, xnorm2, qnorm2, \
+                                                       alive, k, row_lo, p.qt, p.span, p.cap, out_v, out_i); \
+    return CFC_CHECK_LAUNCH();
+  switch (dim / 32) {
+    KM(4) KM(8) KM(12) KM(16) KM(24) KM(32)
+    default: return -2;
+  }
+#undef KM
 }
 
 // rows per IVF list chunk (one workgroup each)

@@ -4,7 +4,8 @@
 [nq, N] scores never reach HBM).  ``--ivf NLIST NPROBE``: the same index as IVF-flat over
 clustered data (a Gaussian mixture, so lists mean something), k-means on a bf16 sample, one
 fused launch per query batch; reports build time, ms per batch and recall@10 against the flat
-scan.
+scan.  ``--many``: batches of 17-128 queries through the many-query kernel, timed beside the loop of
+16-query scans and the library GEMM + top-k (rows appended to ``--out``, default profiles/knn_many.jsonl).
 
 The vectors are generated on the GPU (random, L2-normalised) straight into the index storage;
 queries are batches of <= 16 (the scan kernel's query tile).  Reports scan bandwidth, query
@@ -21,10 +22,59 @@ import torch  # noqa: E402
 from copilot_for_consensus_amd.vectorstore import HipFlatIndex  # noqa: E402
 
 
+def bench_many(idx, n, dim, queries, out, iters=5):
+    """``--many``: batches of 17-128 queries three ways in one process, alternating per iteration:
+    the loop of 16-query fused scans, the library GEMM + K.topk over the [nq, N] score matrix, and
+    the many-query kernel (K.knn_topk with the whole batch).  Median ms of ``iters`` device-event
+    timings each; index_TBs = index bytes / time (what a single pass would stream)."""
+    from copilot_for_consensus_amd.ops import kernels as K
+    X = idx._X[:n]
+
+    def loop16(Q, k):
+        return [K.knn_topk(idx._X, Q[s:s + 16], k, N=n) for s in range(0, Q.shape[0], 16)]
+
+    def gemm(Q, k):
+        return K.topk((Q @ X.T).float().contiguous(), k)
+
+    def many(Q, k):
+        return K.knn_topk(idx._X, Q, k, N=n)
+
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    paths = {"loop16": loop16, "gemm_topk": gemm, "many": many}
+    with open(out, "a") as fh:
+        for k in (10, 150):
+            for nq in (17, 32, 64, 128):
+                Q = queries(nq).bfloat16().contiguous()
+                use = {name: f for name, f in paths.items() if name != "gemm_topk" or nq * n * 6 < 120e9}
+                ms = {name: [] for name in use}
+                for it in range(iters + 1):                  # iteration 0 warms every path up
+                    for name, f in use.items():
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        f(Q, k)
+                        b.record()
+                        b.synchronize()
+                        if it:
+                            ms[name].append(a.elapsed_time(b))
+                ref_i = torch.cat([i for _, i in loop16(Q, k)]).sort(1).values
+                row = {"n": n, "dim": dim, "nq": nq, "k": k,
+                       "same_ids_as_loop16": float((many(Q, k)[1].sort(1).values == ref_i).float().mean())}
+                for name, t in ms.items():
+                    med = sorted(t)[len(t) // 2]
+                    row[name + "_ms"] = round(med, 3)
+                    row[name + "_spread_ms"] = [round(min(t), 3), round(max(t), 3)]
+                    row[name + "_index_TBs"] = round(n * dim * 2 / med / 1e9, 2)
+                print(json.dumps(row), flush=True)
+                fh.write(json.dumps(row) + "\n")
+                fh.flush()
+
+
 def main():
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("n", nargs="?", type=float, default=100_000_000)
+    ap.add_argument("--many", action="store_true", help="time batches of 17-128 queries three ways")
+    ap.add_argument("--out", default="profiles/knn_many.jsonl", help="jsonl the --many rows are appended to")
     ap.add_argument("--ivf", type=int, nargs=2, metavar=("NLIST", "NPROBE"), default=None)
     ap.add_argument("--clusters", type=int, default=20000)
     args = ap.parse_args()
@@ -69,6 +119,8 @@ def main():
             return torch.nn.functional.normalize(torch.randn(nq, dim, device="cuda", generator=g), dim=1)
         c = centers[torch.randint(0, args.clusters, (nq,), device="cuda", generator=g)]
         return torch.nn.functional.normalize(c + 0.02 * torch.randn(nq, dim, device="cuda", generator=g), dim=1)
+    if args.many:
+        return bench_many(idx, n, dim, queries, args.out)
     for nq, k in ((1, 10), (1, 150), (16, 10), (16, 150)):
         Q = queries(nq)
         for _ in range(2):
