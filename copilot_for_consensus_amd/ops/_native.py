@@ -66,6 +66,9 @@ _KERNEL_SIGS = {
     "cfc_knn_topk_many": [P, P, I, I, I, I, P, P, P, I, P, P, P],
     "cfc_knn_many_plan": [I, I, I, c_int64, P],
     "cfc_ivf_topk": [P, P, I, I, I, P, P, P, P, I, P, I, I, P, P, P],
+    "cfc_quant_i8_rows": [P, P, P, P, I, I, I, P],
+    "cfc_knn8_topk": [P, P, P, P, I, I, I, I, P, P, P, I, P, P, P],
+    "cfc_knn8_plan": [I, I, I, c_int64, P],
     "cfc_topk_chunk_size": [],
     "cfc_l2_normalize": [P, P, P, I, I, P],
     "cfc_pool": [P, P, P, P, I, I, I, I, P],

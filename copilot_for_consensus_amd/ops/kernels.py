@@ -2350,6 +2350,57 @@ def knn_topk(X, Q, k: int, xnorm2=None, qnorm2=None, alive=None, row_lo: int = 0
     return _merge_candidates(cv, ci, min(k, N - row_lo))
 
 
+def quant_i8_rows(x: torch.Tensor, normalize: bool = False):
+    """Per-row int8 scalar quantisation of bf16 rows (knn8.hip): (codes int8 [n, D], scale fp32 [n],
+    norm2 fp32 [n] of the decoded rows) with row ~= codes * scale; ``normalize``: unit decoded rows."""
+    if not x.is_cuda:
+        return ref.quant_i8_rows(x, normalize)
+    _req(x, torch.bfloat16, "x")
+    n, dim = x.shape
+    codes = torch.empty(n, dim, dtype=torch.int8, device=x.device)
+    scale = torch.empty(n, dtype=torch.float32, device=x.device)
+    norm2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(kernels().cfc_quant_i8_rows(codes.data_ptr(), scale.data_ptr(), norm2.data_ptr(), x.contiguous().data_ptr(),
+                                      n, dim, 1 if normalize else 0, _stream(x)), "cfc_quant_i8_rows")
+    return codes, scale, norm2
+
+
+def knn_topk_i8(X8, xscale, Q8, qscale, k: int, xnorm2=None, qnorm2=None, alive=None, row_lo: int = 0,
+                N: int | None = None):
+    """Fused scan + top-k over rows [row_lo, N) of an int8 index (codes X8, per-row ``xscale``) for int8
+    queries, k <= 256, on knn8.hip's int8-MFMA kernel: (scores [nq, k] descending, row indices [nq, k]).
+    score = (float(int dot) * qscale[q]) * xscale[row]; with norms, minus the squared L2 distance of the
+    decoded vectors.  More than 16 queries run as 16-query slices.  Dead rows never come back: with
+    fewer than k live rows the tail is -inf / -1."""
+    N = X8.shape[0] if N is None else N
+    nq, dim = Q8.shape
+    kk = min(k, N - row_lo)
+    if not X8.is_cuda:
+        sc = ref.knn_scores_i8(X8[row_lo:N], xscale[row_lo:N], Q8, qscale,
+                               None if xnorm2 is None else xnorm2[row_lo:N], qnorm2)
+        if alive is not None:
+            sc = sc.masked_fill(~alive[row_lo:N].bool()[None], float("-inf"))
+        v, i = torch.topk(sc, kk, dim=1)
+        return v, i + row_lo
+    _req(X8, torch.int8, "X8")
+    _req(Q8, torch.int8, "Q8")
+    if nq > 16:
+        parts = [knn_topk_i8(X8, xscale, Q8[s:s + 16], qscale[s:s + 16], k, xnorm2,
+                             None if qnorm2 is None else qnorm2[s:s + 16], alive, row_lo, N)
+                 for s in range(0, nq, 16)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+    plan = torch.empty(3, dtype=torch.int32)          # span rows, slots per query, spans
+    check(kernels().cfc_knn8_plan(nq, k, dim, N - row_lo, plan.data_ptr()), "cfc_knn8_plan")
+    spans = int(plan[2])
+    cv = torch.empty(nq, spans * k, dtype=torch.float32, device=X8.device)
+    ci = torch.empty(nq, spans * k, dtype=torch.int64, device=X8.device)
+    Q8, qscale = Q8.contiguous(), qscale.contiguous()
+    check(kernels().cfc_knn8_topk(X8.data_ptr(), xscale.data_ptr(), Q8.data_ptr(), qscale.data_ptr(), N, row_lo, nq,
+                                  dim, _p(xnorm2), _p(qnorm2), _p(alive), k, cv.data_ptr(), ci.data_ptr(),
+                                  _stream(X8)), "cfc_knn8_topk")
+    return _merge_candidates(cv, ci, kk)
+
+
 def ivf_topk(X, Q, probe: torch.Tensor, list_off: torch.Tensor, maxc: int, k: int, xnorm2=None, qnorm2=None,
              alive=None):
     """IVF scan of the probed lists, one launch for every (query, probe, chunk): candidates

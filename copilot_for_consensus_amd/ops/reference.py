@@ -430,6 +430,36 @@ def knn_scores(X, Q, xnorm2=None, qnorm2=None):
     return -(xnorm2.float()[None, :] + qnorm2.float()[:, None] - 2 * dots)
 
 
+def quant_i8_rows(x, normalize=False):
+    """Per-row int8 scalar quantisation (knn8.hip cfc_quant_i8_rows): (codes int8 [n, D], scale fp32
+    [n], norm2 fp32 [n]) with row ~= codes * scale.  code = clamp(rint(x * (127 / amax)), +-127);
+    scale = amax / 127, or 1 / sqrt(sum code^2) with ``normalize`` (the decoded row has unit length)."""
+    xf = x.float()
+    amax = xf.abs().amax(1)
+    nz = amax > 0
+    c127 = torch.full_like(amax, 127.0)       # tensor / tensor: one correctly rounded division (a Python
+    inv = torch.where(nz, c127 / amax, torch.zeros_like(amax))      # scalar operand multiplies by a reciprocal)
+    codes = torch.round(xf * inv[:, None]).clamp_(-127, 127)            # torch.round: ties to even
+    S = codes.to(torch.int64).pow(2).sum(1).float()
+    if normalize:
+        scale = torch.where(nz, 1.0 / torch.sqrt(S), torch.zeros_like(S))
+        norm2 = nz.float()
+    else:
+        scale = amax / c127
+        norm2 = S * scale * scale
+    return codes.to(torch.int8), scale, norm2
+
+
+def knn_scores_i8(X8, xscale, Q8, qscale, xnorm2=None, qnorm2=None):
+    """Scores [nq, N] of int8 rows: the exact integer dot product, then the same two fp32 multiplies
+    as knn8.hip: (float(dot) * qscale[q]) * xscale[row]; with norms, -(xnorm2 + qnorm2 - 2 score)."""
+    dots = (Q8.cpu().to(torch.int64) @ X8.cpu().to(torch.int64).T).to(device=X8.device, dtype=torch.float32)
+    s = (dots * qscale.float()[:, None]) * xscale.float()[None, :]
+    if xnorm2 is None:
+        return s
+    return -(xnorm2.float()[None, :] + qnorm2.float()[:, None] - 2 * s)
+
+
 def l2_normalize(x):
     xf = x.float()
     n2 = xf.pow(2).sum(-1)

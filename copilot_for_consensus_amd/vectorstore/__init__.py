@@ -11,6 +11,9 @@ count / get).  Replaces Qdrant / FAISS / Azure AI Search on the hot path (SURVEY
   fused MFMA scan kernel, larger batches a hipBLASLt GEMM; exact top-k by the radix-select kernel.
   Vectors produced on the GPU (the encoder) are inserted without a host round trip.
   Upserts overwrite in place; deletes tombstone + periodic compaction.
+  ``vector_dtype="int8"``: scalar quantisation (Qdrant ``scalar.type = int8`` / FAISS ``QT_8bit``): int8
+  codes + one fp32 scale per row, half the HBM of bf16, scanned by the int8-MFMA kernel (knn8.hip);
+  search is exact on the decoded rows and decoded queries.
 * :class:`HipIVFIndex` -- IVF-flat: k-means coarse quantiser trained on the GPU, rows stored
   list-contiguous, ``nprobe`` lists scanned per query.
 * :class:`InMemoryVectorStore` -- numpy reference (fixes the reference's duplicate-id error,
@@ -178,18 +181,27 @@ class HipFlatIndex(VectorStore):
     """Exact flat index resident in HBM (see module docstring)."""
 
     def __init__(self, dimension: int = 384, distance: str = "cosine", capacity: int = 1 << 16, device="cuda",
-                 faiss_scores: bool = False, **_):
+                 faiss_scores: bool = False, vector_dtype: str = "bf16", **_):
         if distance not in ("cosine", "dot", "l2", "euclid"):
             raise ValueError(f"unknown distance {distance!r}")
         if int(dimension) <= 0:
             raise ValueError(f"dimension must be positive, got {dimension}")
+        if vector_dtype not in ("bf16", "int8"):
+            raise ValueError(f"unknown vector_dtype {vector_dtype!r} (bf16 or int8)")
+        if vector_dtype == "int8" and int(dimension) not in (128, 256, 384, 512, 768, 1024):
+            raise ValueError(f"an int8 index needs dimension 128, 256, 384, 512, 768 or 1024, got {dimension}")
+        # "int8": rows are int8 codes + one fp32 scale each (scalar quantisation, half the bytes of
+        # bf16), scanned by knn8.hip; a row's value everywhere else is the decoded code * scale
+        self.vector_dtype = vector_dtype
+        self._xdtype = torch.int8 if vector_dtype == "int8" else torch.bfloat16
         self.dim = int(dimension)
         self.metric = "l2" if distance in ("l2", "euclid") else distance
         self.faiss_scores = faiss_scores
         self.device = torch.device(device if (device != "cuda" or torch.cuda.is_available()) else "cpu")
         self._cap = 0
         self._n = 0                       # rows in use (incl. tombstones)
-        self._X = torch.empty(0, self.dim, dtype=torch.bfloat16, device=self.device)
+        self._X = torch.empty(0, self.dim, dtype=self._xdtype, device=self.device)
+        self._scale = torch.empty(0, dtype=torch.float32, device=self.device)     # int8 mode only
         self._norm2 = torch.empty(0, dtype=torch.float32, device=self.device)
         self._alive = torch.empty(0, dtype=torch.bool, device=self.device)
         # ids + metadata: numpy columns and byte heaps, no Python object per row (rowtable.py)
@@ -203,34 +215,52 @@ class HipFlatIndex(VectorStore):
         if n <= self._cap:
             return
         cap = max(n, 2 * self._cap, 1024)
-        X = torch.zeros(cap, self.dim, dtype=torch.bfloat16, device=self.device)
+        X = torch.zeros(cap, self.dim, dtype=self._xdtype, device=self.device)
         n2 = torch.zeros(cap, dtype=torch.float32, device=self.device)
         al = torch.zeros(cap, dtype=torch.bool, device=self.device)
+        sc = torch.zeros(cap if self.vector_dtype == "int8" else 0, dtype=torch.float32, device=self.device)
         # rows already written (add_embeddings counts new rows in _n before it reserves them)
         k = min(self._n, self._cap)
         if k:
             X[:k] = self._X[:k]
             n2[:k] = self._norm2[:k]
             al[:k] = self._alive[:k]
-        self._X, self._norm2, self._alive, self._cap = X, n2, al, cap
+            if sc.numel():
+                sc[:k] = self._scale[:k]
+        self._X, self._norm2, self._alive, self._scale, self._cap = X, n2, al, sc, cap
 
-    def _prepare(self, vecs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    def _rows(self, X: torch.Tensor, scale: torch.Tensor | None) -> torch.Tensor:
+        """Row values as stored: bf16 rows as they are, int8 rows decoded to fp32 code * scale."""
+        return X if self.vector_dtype == "bf16" else X.float() * scale[:, None]
+
+    def _row(self, r: int) -> list[float]:
+        return self._rows(self._X[r:r + 1], self._scale[r:r + 1])[0].float().cpu().tolist()
+
+    def _gather(self, idx: torch.Tensor) -> torch.Tensor:
+        return self._rows(self._X.index_select(0, idx),
+                          self._scale.index_select(0, idx) if self.vector_dtype == "int8" else None)
+
+    def _prepare(self, vecs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor | None]:
+        """Rows as stored, their squared norms, and (int8 mode) their scales."""
         from ..ops import kernels as K
         v = vecs.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        if self.vector_dtype == "int8":
+            codes, scale, n2 = K.quant_i8_rows(v, normalize=self.metric == "cosine")
+            return codes, n2, scale
         n2 = torch.empty(v.shape[0], dtype=torch.float32, device=self.device)
         if self.metric == "cosine":
             v = K.l2_normalize(v, norms2=n2)
             n2.fill_(1.0)
         else:
             n2 = v.float().pow(2).sum(1)
-        return v, n2
+        return v, n2, None
 
     def add_embeddings(self, ids, vectors, metadatas=None):
         vecs = _as_matrix(vectors, self.dim)
         if len(ids) != vecs.shape[0]:
             raise ValueError("ids and vectors length mismatch")
         metadatas = list(metadatas) if metadatas is not None else [{} for _ in ids]
-        v, n2 = self._prepare(vecs)
+        v, n2, sc = self._prepare(vecs)
         with self._lock:
             rows = self._tab.upsert(ids, metadatas)
             self._n = self._tab.n
@@ -238,6 +268,8 @@ class HipFlatIndex(VectorStore):
             idx = torch.from_numpy(rows).to(self.device)
             self._X.index_copy_(0, idx, v)
             self._norm2.index_copy_(0, idx, n2)
+            if sc is not None:
+                self._scale.index_copy_(0, idx, sc)
             self._alive[idx] = True
 
     def add_bulk(self, ids, vectors, metadatas=None) -> None:
@@ -253,9 +285,11 @@ class HipFlatIndex(VectorStore):
             self._n = self._tab.n
             self._reserve(self._n)
             for s in range(0, vecs.shape[0], 1 << 22):
-                v, n2 = self._prepare(vecs[s:s + (1 << 22)])
+                v, n2, sc = self._prepare(vecs[s:s + (1 << 22)])
                 self._X[n0 + s:n0 + s + v.shape[0]] = v
                 self._norm2[n0 + s:n0 + s + v.shape[0]] = n2
+                if sc is not None:
+                    self._scale[n0 + s:n0 + s + v.shape[0]] = sc
             self._alive[n0:self._n] = True
 
     def has(self, id) -> bool:
@@ -281,6 +315,8 @@ class HipFlatIndex(VectorStore):
             n = int(keep.size)
             self._X[:n] = self._X.index_select(0, idx) if n else self._X[:0]
             self._norm2[:n] = self._norm2.index_select(0, idx) if n else self._norm2[:0]
+            if self.vector_dtype == "int8" and n:
+                self._scale[:n] = self._scale.index_select(0, idx)
             self._alive[:n] = True
             self._alive[n:] = False
             self._tab.permute(keep)
@@ -299,7 +335,7 @@ class HipFlatIndex(VectorStore):
         r = self._tab.find(id)
         if r < 0:
             raise KeyError(id)
-        return SearchResult(id, 1.0, self._X[r].float().cpu().tolist(), self._tab.meta_at(r))
+        return SearchResult(id, 1.0, self._row(r), self._tab.meta_at(r))
 
     # ------------------------------------------------------------------ search
     def centroid_scores(self, ids):
@@ -310,7 +346,7 @@ class HipFlatIndex(VectorStore):
             if not have:
                 return {}
             idx = torch.from_numpy(rows[rows >= 0]).to(self.device)
-            s = self.span_centroid_scores(self._X.index_select(0, idx), [(0, len(have))])
+            s = self.span_centroid_scores(self._gather(idx), [(0, len(have))])
             return dict(zip(have, s.cpu().tolist()))
 
     def centroid_scores_many(self, groups):
@@ -331,7 +367,7 @@ class HipFlatIndex(VectorStore):
                 return [{} for _ in groups]
             idx = torch.from_numpy(np.concatenate(rows_all)).to(self.device)
             live = [(a, b) for a, b in spans if b > a]
-            s = self.span_centroid_scores(self._X.index_select(0, idx), live).cpu().tolist()
+            s = self.span_centroid_scores(self._gather(idx), live).cpu().tolist()
         return [dict(zip(h, s[a:b])) for h, (a, b) in zip(have, spans)]
 
     @staticmethod
@@ -355,6 +391,8 @@ class HipFlatIndex(VectorStore):
         nq = Q.shape[0]
         if hi <= lo:
             return (torch.empty(nq, 0, device=self.device), torch.empty(nq, 0, dtype=torch.long, device=self.device))
+        if self.vector_dtype == "int8":
+            return self._search_i8(Q.contiguous(), k, lo, hi)
         X = self._X[lo:hi]
         if self.metric == "cosine":
             Qn = K.l2_normalize(Q.contiguous())
@@ -378,6 +416,30 @@ class HipFlatIndex(VectorStore):
         v, i = K.topk(scores.contiguous(), k)
         return v, i + lo
 
+    def _search_i8(self, Q: torch.Tensor, k: int, lo: int, hi: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """search() of an int8 index: the queries are quantised like the rows, so a score is the dot
+        product (or minus the squared distance) of the DECODED query and row."""
+        from ..ops import kernels as K
+        Q8, qs, qn2 = K.quant_i8_rows(Q, normalize=self.metric == "cosine")
+        l2 = self.metric == "l2"
+        alive = self._alive if self._dead else None
+        if not Q.is_cuda or k <= 256:
+            return K.knn_topk_i8(self._X, self._scale, Q8, qs, k, self._norm2 if l2 else None, qn2 if l2 else None,
+                                 alive, row_lo=lo, N=hi)
+        # k > 256 (not a hot path): scores of the decoded rows, 1M rows at a time, then the radix select
+        Qd = Q8.float() * qs[:, None]
+        scores = torch.empty(Q.shape[0], hi - lo, dtype=torch.float32, device=self.device)
+        for s in range(lo, hi, 1 << 20):
+            e = min(hi, s + (1 << 20))
+            sc = Qd @ self._rows(self._X[s:e], self._scale[s:e]).T
+            if l2:
+                sc = -(self._norm2[s:e][None, :] + qn2[:, None] - 2 * sc)
+            scores[:, s - lo:e - lo] = sc
+        if alive is not None:
+            scores.masked_fill_(~alive[lo:hi][None, :], float("-inf"))
+        v, i = K.topk(scores, k)
+        return v, i + lo
+
     def _to_results(self, v: torch.Tensor, i: torch.Tensor, with_vectors: bool = True) -> list[list[SearchResult]]:
         v, i = v.cpu(), i.cpu()
         out = []
@@ -389,7 +451,7 @@ class HipFlatIndex(VectorStore):
                     continue
                 if self.metric == "l2":
                     s = 1.0 / (1.0 + max(0.0, -s)) if self.faiss_scores else -s
-                vec = self._X[r].float().cpu().tolist() if with_vectors else []
+                vec = self._row(r) if with_vectors else []
                 res.append(SearchResult(rid, float(s), vec, self._tab.meta_at(r)))
             out.append(res)
         return out
@@ -420,10 +482,13 @@ class HipFlatIndex(VectorStore):
         p.mkdir(parents=True, exist_ok=True)
         with self._lock:
             self.compact()
-            save_file({"vectors": self._X[:self._n].contiguous().cpu(), "norm2": self._norm2[:self._n].cpu()},
-                      str(p / "vectors.safetensors"))
+            blob = {"vectors": self._X[:self._n].contiguous().cpu(), "norm2": self._norm2[:self._n].cpu()}
+            if self.vector_dtype == "int8":
+                blob["scale"] = self._scale[:self._n].cpu()
+            save_file(blob, str(p / "vectors.safetensors"))
             self._tab.save(p)
-            hdr = {"dim": self.dim, "metric": self.metric, "rows": self._n, "format": "rowtable-1"}
+            hdr = {"dim": self.dim, "metric": self.metric, "rows": self._n, "format": "rowtable-1",
+                   "vector_dtype": self.vector_dtype}
             hdr.update(self._extra_header())
             (p / "index.json").write_text(json.dumps(hdr))
             extra = self._extra_tensors()
@@ -446,9 +511,12 @@ class HipFlatIndex(VectorStore):
         meta = json.loads((p / "index.json").read_text())
         t = load_file(str(p / "vectors.safetensors"))
         n = int(meta["rows"]) if "rows" in meta else len(meta["ids"])
-        idx = cls(meta["dim"], "l2" if meta["metric"] == "l2" else meta["metric"], capacity=n + 1024, device=device)
+        idx = cls(meta["dim"], "l2" if meta["metric"] == "l2" else meta["metric"], capacity=n + 1024, device=device,
+                  vector_dtype=meta.get("vector_dtype", "bf16"))     # shards from before the field are bf16
         idx._X[:n] = t["vectors"].to(idx.device)
         idx._norm2[:n] = t["norm2"].to(idx.device)
+        if idx.vector_dtype == "int8":
+            idx._scale[:n] = t["scale"].to(idx.device)
         idx._alive[:n] = True
         if meta.get("format") == "rowtable-1":
             idx._tab = RowTable.load(p)
@@ -481,6 +549,8 @@ class HipIVFIndex(HipFlatIndex):
     ASSIGN_CHUNK = 1 << 20
 
     def __init__(self, dimension=384, distance="cosine", nlist: int = 0, nprobe: int = 8, **kw):
+        if kw.get("vector_dtype", "bf16") != "bf16":
+            raise ValueError("HipIVFIndex stores bf16 rows only (vector_dtype='int8' is a flat-index mode)")
         super().__init__(dimension, distance, **kw)
         self.nlist, self.nprobe = int(nlist), int(nprobe)
         self.centroids: torch.Tensor | None = None

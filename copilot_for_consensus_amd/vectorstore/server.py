@@ -8,7 +8,8 @@ serves the subset of Qdrant's REST API the reference's driver uses -- the same U
 ``VECTOR_STORE_TYPE=qdrant`` (vectorstore/remote.py, or the reference's qdrant-client) pointed at
 this server runs its searches on the MI355X:
 
-  GET/PUT/DELETE /collections/{name}            (vectors.size, vectors.distance Cosine | Euclid | Dot)
+  GET/PUT/DELETE /collections/{name}            (vectors.size, vectors.distance Cosine | Euclid | Dot;
+                                                 quantization_config.scalar.type int8 -> int8 flat index)
   PUT  /collections/{name}/points               upsert {"points": [{"id", "vector", "payload"}]}
   POST /collections/{name}/points/search        {"vector", "limit", "with_payload", "with_vector", "score_threshold"}
   POST /collections/{name}/points/search/batch  {"searches": [...]}   (one fused kNN launch per 16 queries)
@@ -54,19 +55,22 @@ def _err(code: int, msg: str) -> JSONResponse:
 
 class _Collection:
     def __init__(self, name: str, size: int, distance: str, device: str, capacity: int, index_type: str,
-                 nlist: int, nprobe: int):
+                 nlist: int, nprobe: int, quantization: dict | None = None):
         from . import HipFlatIndex, HipIVFIndex
         self.name, self.size, self.distance = name, int(size), distance
+        self.quantization = quantization          # Qdrant's quantization_config ({"scalar": {"type": "int8"}}) or None
         metric = _DIST[distance.lower()]
         if index_type == "ivf":
             self.index = HipIVFIndex(self.size, metric, nlist=nlist, nprobe=nprobe, capacity=capacity, device=device)
         else:
-            self.index = HipFlatIndex(self.size, metric, capacity=capacity, device=device)
+            self.index = HipFlatIndex(self.size, metric, capacity=capacity, device=device,
+                                      vector_dtype="int8" if quantization else "bf16")
 
     def info(self) -> dict:
         return {"status": "green", "points_count": self.index.count(), "vectors_count": self.index.count(),
                 "indexed_vectors_count": self.index.count(),
-                "config": {"params": {"vectors": {"size": self.size, "distance": self.distance}}}}
+                "config": {"params": {"vectors": {"size": self.size, "distance": self.distance}},
+                           "quantization_config": self.quantization}}
 
     def score(self, s: float) -> float:
         return math.sqrt(max(0.0, s)) if self.distance.lower() == "euclid" else s
@@ -95,7 +99,8 @@ def create_vector_app(device: str = "cuda", capacity: int = 1 << 20, index_type:
             meta = json.loads((d / "collection.json").read_text())
             if not _VALID_NAME.match(str(meta.get("name", ""))) or meta["name"] != d.name:
                 continue   # a hand-edited or foreign directory: never let it name a path
-            c = _Collection(meta["name"], meta["size"], meta["distance"], device, 1024, "flat", 0, 8)
+            c = _Collection(meta["name"], meta["size"], meta["distance"], device, 1024, "flat", 0, 8,
+                            meta.get("quantization_config"))
             if (d / "index.json").exists():
                 c.index = HipFlatIndex.load(d, device=device)
             cols[meta["name"]] = c
@@ -106,7 +111,8 @@ def create_vector_app(device: str = "cuda", capacity: int = 1 << 20, index_type:
         import json
         d = coll_dir(c.name)
         c.index.save(d)
-        (d / "collection.json").write_text(json.dumps({"name": c.name, "size": c.size, "distance": c.distance}))
+        (d / "collection.json").write_text(json.dumps({"name": c.name, "size": c.size, "distance": c.distance,
+                                                         "quantization_config": c.quantization}))
 
     load_persisted()
     app.state.save_all = lambda: [save(c) for c in list(cols.values())]
@@ -184,10 +190,21 @@ def create_vector_app(device: str = "cuda", capacity: int = 1 << 20, index_type:
             return _err(400, "vectors.size must be a positive int and distance one of Cosine, Euclid, Dot")
         if not _VALID_NAME.match(name):
             return _err(400, f"invalid collection name {name!r}: expected [A-Za-z0-9_-]{{1,255}}")
+        quant = body.get("quantization_config")
+        if quant is not None:
+            # scalar int8 only: the int8 flat index (codes + one scale per row, knn8.hip)
+            qtype = (quant.get("scalar") or {}).get("type") if isinstance(quant, dict) else None
+            if qtype != "int8":
+                return _err(400, "quantization_config: only {\"scalar\": {\"type\": \"int8\"}} is supported")
+            if index_type == "ivf":
+                return _err(400, "quantization_config needs a flat index (this server runs index_type=ivf)")
+            if size not in (128, 256, 384, 512, 768, 1024):
+                return _err(400, "int8 quantization needs vectors.size 128, 256, 384, 512, 768 or 1024")
+            quant = {"scalar": {"type": "int8"}}
         with lock:
             if name in cols:
                 return _err(409, f"Collection `{name}` already exists!")
-            cols[name] = _Collection(name, size, dist.capitalize(), device, capacity, index_type, nlist, nprobe)
+            cols[name] = _Collection(name, size, dist.capitalize(), device, capacity, index_type, nlist, nprobe, quant)
         return _ok(True, t0)
 
     @app.delete("/collections/{name}")

@@ -6,6 +6,8 @@ clustered data (a Gaussian mixture, so lists mean something), k-means on a bf16 
 fused launch per query batch; reports build time, ms per batch and recall@10 against the flat
 scan.  ``--many``: batches of 17-128 queries through the many-query kernel, timed beside the loop of
 16-query scans and the library GEMM + top-k (rows appended to ``--out``, default profiles/knn_many.jsonl).
+``--vector-dtype both``: the int8 scalar-quantised flat index beside the bf16 one over the same clustered
+rows (time, resident bytes, recall@10 of int8 against bf16; default ``--out`` profiles/knn_int8.jsonl).
 
 The vectors are generated on the GPU (random, L2-normalised) straight into the index storage;
 queries are batches of <= 16 (the scan kernel's query tile).  Reports scan bandwidth, query
@@ -69,9 +71,74 @@ def bench_many(idx, n, dim, queries, out, iters=5):
                 fh.flush()
 
 
+def bench_dtypes(n, dim, clusters, dtypes, out, iters=7):
+    """``--vector-dtype``: the flat scan of an int8 index (knn8.hip) beside the bf16 one over the SAME
+    rows (a Gaussian mixture, quantised from the bf16 rows) in one process, alternating per iteration.
+    Median ms of ``iters`` device-event timings of idx.search (query preparation, scan and merge);
+    index_TBs = the index's resident vector bytes / time; recall@10 of int8 against the bf16 result."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    centers = torch.nn.functional.normalize(torch.randn(clusters, dim, device="cuda", generator=g), dim=1)
+    idx = {d: HipFlatIndex(dim, device="cuda", capacity=n, vector_dtype=d) for d in dtypes}
+    for s in range(0, n, 1 << 22):
+        e = min(n, s + (1 << 22))
+        v = centers[torch.randint(0, clusters, (e - s,), device="cuda", generator=g)] \
+            + 0.02 * torch.randn(e - s, dim, device="cuda", generator=g)
+        for ix in idx.values():
+            rows, n2, sc = ix._prepare(v)
+            ix._X[s:e], ix._norm2[s:e] = rows, n2
+            if sc is not None:
+                ix._scale[s:e] = sc
+        del v
+    for ix in idx.values():
+        ix._alive[:n] = True
+        ix._n = n
+    nbytes = {d: n * dim * (1 if d == "int8" else 2) + (n * 4 if d == "int8" else 0) for d in dtypes}
+
+    def queries(nq):
+        c = centers[torch.randint(0, clusters, (nq,), device="cuda", generator=g)]
+        return c + 0.02 * torch.randn(nq, dim, device="cuda", generator=g)
+
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "a") as fh:
+        for nq, k in ((1, 10), (1, 150), (16, 10), (16, 150)):
+            Q = queries(nq)
+            ms = {d: [] for d in dtypes}
+            for it in range(iters + 2):                      # iterations 0 and 1 warm both paths up
+                for d, ix in idx.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    ix.search(Q, k)
+                    b.record()
+                    b.synchronize()
+                    if it > 1:
+                        ms[d].append(a.elapsed_time(b))
+            row = {"n": n, "dim": dim, "nq": nq, "k": k}
+            for d, t in ms.items():
+                med = sorted(t)[len(t) // 2]
+                row[d + "_ms"] = round(med, 3)
+                row[d + "_spread_ms"] = [round(min(t), 3), round(max(t), 3)]
+                row[d + "_index_TBs"] = round(nbytes[d] / med / 1e9, 2)
+                row[d + "_resident_bytes"] = nbytes[d]
+            print(json.dumps(row), flush=True)
+            fh.write(json.dumps(row) + "\n")
+            fh.flush()
+        if len(dtypes) == 2:
+            Q = queries(64)
+            hits = 0
+            for s in range(0, 64, 16):
+                i8 = idx["int8"].search(Q[s:s + 16], 10)[1].cpu().tolist()
+                ib = idx["bf16"].search(Q[s:s + 16], 10)[1].cpu().tolist()
+                hits += sum(len(set(x) & set(y)) for x, y in zip(i8, ib))
+            row = {"n": n, "dim": dim, "int8_recall_at_10_vs_bf16": round(hits / 640, 4)}
+            print(json.dumps(row), flush=True)
+            fh.write(json.dumps(row) + "\n")
+
+
 def main():
     import argparse
     ap = argparse.ArgumentParser()
+    ap.add_argument("--vector-dtype", choices=("bf16", "int8", "both"), default=None,
+                    help="time the flat scan of an int8 index, a bf16 one, or both over the same clustered rows")
     ap.add_argument("n", nargs="?", type=float, default=100_000_000)
     ap.add_argument("--many", action="store_true", help="time batches of 17-128 queries three ways")
     ap.add_argument("--out", default="profiles/knn_many.jsonl", help="jsonl the --many rows are appended to")
@@ -80,6 +147,10 @@ def main():
     args = ap.parse_args()
     n = int(args.n)
     dim = 384
+    if args.vector_dtype:
+        dtypes = ("bf16", "int8") if args.vector_dtype == "both" else (args.vector_dtype,)
+        out = args.out if args.out != ap.get_default("out") else "profiles/knn_int8.jsonl"
+        return bench_dtypes(n, dim, args.clusters, dtypes, out)
     if args.ivf:
         from copilot_for_consensus_amd.vectorstore import HipIVFIndex
         idx = HipIVFIndex(dim, "cosine", nlist=args.ivf[0], nprobe=args.ivf[1], device="cuda", capacity=n)
